@@ -18,9 +18,22 @@ pivots/s = steps x K / time; `ms_per_step` is the time of one block. Warm-up
 steps are whole blocks too, so every timed pass applies exactly K pending
 pivots (the kernel and K named in `roofline`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the steps, print the line. `--full` adds the legs that take runs or
+readouts of their own: the CPU baseline and its pivot-sequence comparison
+(`cpu_baseline`, `parity`), the pinned-trajectory comparisons
+(`parity_trajectory`, config 5's `parity_fixture`) and config 2's
+event-instrumented blocks (its `roofline` timing; configs 3 and 4 time the
+pass with events inside the timed region, in either form).
+
+`--dump-outputs DIR` writes what the timed region left behind, as a caller of
+the engine would read it back after the last step, to DIR/<name>.npy
+(float64; dump_outputs below). The LP is generated from a fixed seed, so two
+builds run with the same arguments can be compared array for array.
 
 With N > 1 the tableau is row-block partitioned over N processes (one per
 GPU; strong scaling: the LP is the same for every N). Per pivot the owner of
@@ -35,7 +48,7 @@ launch of the dominant kernel on rank 0 (k_flushw: 16 B x local constraint
 rows x columns not skipped, one read + one write of every entry the block
 changes; eager k_update: the same over all rows for one pivot) / its mean
 device time, timed with HIP events around that kernel alone on the engine's
-own stream over the timed region. `cpu_baseline` =
+own stream over the timed region. `cpu_baseline` (with --full) =
 the CPU oracle (oracle/liblpo.so, same pivot rules, OpenMP) on the same LP,
 rank 0 at N=1 only, for a bounded number of pivots; its pivot sequence is
 compared with the GPU's.
@@ -187,7 +200,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=16)    # deferred blocks (K pivots each) timed
     ap.add_argument("--warmup", type=int, default=2)    # blocks before the timed region (page-in, graph build)
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: CPU baseline, trajectory / fixture parity, "
+                         "config 2's event-instrumented blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the engine's state as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget")
     ap.add_argument("--cpu-1core-seconds", type=float, default=6.0, help="1-core CPU baseline time budget")
     ap.add_argument("--variant", type=int, default=None, help="eager update-kernel form (LPG_UPDATE_VARIANT 0|1)")
@@ -285,6 +303,51 @@ def trajectory_parity(a, eng, world, rank):
     return cmp if rank == 0 else None
 
 
+DUMP_ROW_BYTES = 40 << 20     # sampled constraint rows; with the vectors below the dump stays under 64 MB
+DUMP_LOG_ENTRIES = 1 << 19    # the last entries of the pivot log (2 x 4 MB at most)
+
+
+def dump_row_sample(m, ncols):
+    """The constraint rows --dump-outputs writes for an m-row, ncols-column
+    tableau: every row when they fit DUMP_ROW_BYTES, else a sorted sample that
+    depends on (m, ncols) alone."""
+    import numpy as np
+    nsample = max(1, min(m, DUMP_ROW_BYTES // (8 * ncols)))
+    return np.sort(np.random.default_rng(SEED).choice(m, size=nsample, replace=False))
+
+
+def dump_outputs(dirpath, eng, res, m, world, rank):
+    """--dump-outputs: what a caller reads back after the last timed step, as
+    float64 DIR/<name>.npy (integers are exact: they are below 2^53). Every
+    rank reads (the readouts flush a pending block), rank 0 writes.
+      result             [status, pivots, objective]
+      log_entering/_leaving   the (entering column, leaving row) log, last DUMP_LOG_ENTRIES pivots
+      basis              basic column of every row
+    and at N = 1, where this rank holds every row:
+      column0            right-hand sides of the constraint rows (x_B)
+      objective_row      the objective value and the reduced costs
+      tableau_rows       constraint rows `tableau_row_index`: all of them when they fit
+                         DUMP_ROW_BYTES, else a sample drawn once from default_rng(SEED), sorted
+    """
+    import numpy as np
+    k, r = eng.get_log()
+    out = {"result": np.array([res.status, res.pivots, res.objective], dtype=np.float64),
+           "log_entering": k[-DUMP_LOG_ENTRIES:].astype(np.float64),
+           "log_leaving": r[-DUMP_LOG_ENTRIES:].astype(np.float64),
+           "basis": eng.get_basis().astype(np.float64)}
+    if world == 1:
+        out["column0"] = eng.get_column0()
+        out["objective_row"] = eng.get_rows(m, 1)[0]
+        idx = dump_row_sample(m, eng.ncols)
+        out["tableau_row_index"] = idx.astype(np.float64)
+        out["tableau_rows"] = np.concatenate([eng.get_rows(int(i), 1) for i in idx])
+    if rank != 0:
+        return
+    os.makedirs(dirpath, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def host_ops(world):
     """gloo host collectives for lpg_comm_init_host (setup and bootstrap only once the push exchange is attached)."""
     import numpy as np
@@ -341,6 +404,11 @@ def config5(a):
                          "full_tableau_bytes_per_launch": eng.info.bytes_per_pivot, "update_ms_mean": upd_ms},
             "status": lpg.STATUS_NAMES.get(res.status, res.status), "pivots_total": res.pivots,
             "objective": res.objective, "seconds": elapsed, "build_stamp": lpg_lib.build_stamp}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, eng, res, m, 1, 0)
+    if not a.full:                   # the plain run ends here: parity and the CPU leg are --full's
+        print(json.dumps(line), flush=True)
+        return
     # the whole solve against the oracle's (tests/golden/config5_solve.json), read after the timed region
     sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
     try:
@@ -521,15 +589,20 @@ def main():
     # HIP events around the block pass inside the timed region (the roofline
     # numerator's kernel time). For config 2 the events would forbid the
     # hipGraph replay that hides its launch overhead, so config 2 times the
-    # pass in an event-instrumented run of 3 blocks before the timed region.
+    # pass in an event-instrumented run of 3 blocks before the timed region
+    # (--full; a plain run takes the same 3 blocks without events, so that the
+    # timed region covers the same pivots either way, and reports no pass time).
     live_events = a.config != 2
+    timing = None
     if not live_events:
-        eng.set_timing(True)
-        eng.get_timing()
+        if a.full:
+            eng.set_timing(True)
+            eng.get_timing()
         eng.enqueue(3 * K, lpg.RULE_DANTZIG)
         eng.sync()
-        timing = eng.get_timing()
-        eng.set_timing(False)
+        if a.full:
+            timing = eng.get_timing()
+            eng.set_timing(False)
         eng.enqueue(4 * K, lpg.RULE_DANTZIG)           # builds the replayed hipGraph outside the timed region
         before = eng.sync().pivots
     eng.set_timing(live_events)
@@ -560,6 +633,9 @@ def main():
         dd = torch.tensor([done], dtype=torch.int64)
         dist.all_reduce(dd, op=dist.ReduceOp.MIN)
         done = int(dd.item())
+    timed_pass = timing is not None
+    if not timed_pass:                  # config 2 without --full: no event-timed pass, the roofline figures stay 0
+        timing = lpg_lib.Timing()
     upd_ms = timing.update_ms / max(timing.update_count, 1)
     # bytes the block pass actually read + wrote (columns whose K pending P
     # entries are all zero are not counted, SURVEY.md §8(d) restated per block
@@ -580,6 +656,8 @@ def main():
             "full_tableau_bytes_per_launch": info.bytes_per_pivot,
             "column_skipping": not a.no_skip,
             "update_ms_mean": upd_ms})
+    if not timed_pass:
+        roof["note"] = "config 2 times its block pass in event-instrumented blocks of their own: run with --full"
     if defer and live_events:
         # per-block ceiling: the pass at the HBM spec peak plus the measured rest of the block (pivot kernels,
         # column trade, pivot-row rewrite, launch gaps), i.e. what this design reaches with a perfect pass
@@ -633,10 +711,12 @@ def main():
         "objective": res.objective,
     }
     line["build_stamp"] = lpg_lib.build_stamp
-    traj = trajectory_parity(a, eng, world, rank)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, eng, res, m, world, rank)
+    traj = trajectory_parity(a, eng, world, rank) if a.full else None
     if traj is not None:
         line["parity_trajectory"] = traj
-    if world == 1 and rank == 0 and not a.no_cpu:
+    if a.full and world == 1 and rank == 0 and not a.no_cpu:
         log = eng.get_log()
         eng.close()
         cb, parity = cpu_baseline(m, n, log, a.cpu_seconds, a.cpu_1core_seconds)

@@ -14,6 +14,8 @@ if [ -z "${SKIP_TESTS:-}" ]; then
 else
   rc=0
 fi
+# the whole bench line (CPU baseline, parity legs), not only the headline figure
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err || exit $?
 for o in ${LATE_ORDERS:-}; do
   timeout -k 10 120 python tools/runtime_order.py $o >> gpurun_out/runtime_order.log 2>&1 || { echo "$o rc=$?" >> gpurun_out/runtime_order.log; exit 3; }

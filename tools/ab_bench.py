@@ -2,7 +2,7 @@
 
     python tools/ab_bench.py "ARGS" "NAME=VAL NAME=VAL" "NAME=VAL" ...   (an empty string = the default build)
 
-Runs `python bench.py ARGS --no-cpu` once per variant, REPS (env, default 2)
+Runs `python bench.py ARGS --full --no-cpu` once per variant, REPS (env, default 2)
 rounds interleaved, each in a fresh process, and prints per run: pivots/s,
 ms per block, the pass's HIP-event mean, its TFLOP/s, and whether the
 trajectory parity held. Each run is limited to T_RUN seconds (default 200).
@@ -25,7 +25,7 @@ def main():
             for kv in v.split():
                 k, val = kv.split("=", 1)
                 env[k] = val
-            p = subprocess.run([sys.executable, "bench.py"] + args + ["--no-cpu"], cwd=ROOT, env=env,
+            p = subprocess.run([sys.executable, "bench.py"] + args + ["--full", "--no-cpu"], cwd=ROOT, env=env,
                                capture_output=True, text=True, timeout=int(os.environ.get("T_RUN", 200)))
             if p.returncode != 0:
                 print(f"[{v or 'default'}] rc={p.returncode}: {p.stderr[-1500:]}", flush=True)

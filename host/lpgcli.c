@@ -26,6 +26,10 @@
  *          any HIP call; the parent only relays the host-staged collectives
  *          over socketpairs and never touches a GPU); rank r on device
  *          (D + r) mod #devices; rank 0 prints the JSON line
+ *   lpgcli --synthetic M N --batch B [--dual] [--rule ...] [--pivots K] [--seed S]
+ *          B LPs of that shape (seeds S, S + 1, ...) in one lpg_batch, one
+ *          workgroup per LP; prints the counts per status, the total pivots
+ *          and the LPs/s and pivots/s of the solve call
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
@@ -60,11 +64,13 @@ static const char *status_name(int s) {
 static int usage(const char *argv0) {
     fprintf(stderr, "Usage:\n\t%s --synthetic M N [--seed S] [--kind dense|degenerate|artificial] [--rule dantzig|bland]"
                     " [--pivots K] [--device D] [--gpus P [--exchange push|host]]\n"
+                    "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate] [--rule dantzig|bland] [--pivots K]"
+                    " [--seed S]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
                     "\t(--dual: the dual simplex; also with --synthetic (any --gpus) and --tableau;\n"
                     "\t --kind artificial: the two-phase method)\n",
-            argv0, argv0, argv0, argv0);
+            argv0, argv0, argv0, argv0, argv0);
     return 2;
 }
 
@@ -319,6 +325,48 @@ static int run_dist(const dist_args *a) {
     return rc;
 }
 
+/* --batch B: B synthetic LPs of one shape through lpg_batch */
+static int run_batch(long long m, long long n, long long count, unsigned long long seed, int kind, int dual, int rule,
+                     long long pivots, int device) {
+    lpg_batch *b = NULL;
+    lpg_result *res = (lpg_result *)malloc((size_t)(count > 0 ? count : 1) * sizeof(lpg_result));
+    if (!res) return 1;
+    if (lpg_batch_create(&b, device, count, m, n + m + 1, 0) != 0 ||
+        lpg_batch_generate(b, n, seed, dual ? LPG_GEN_DUAL : kind) != 0) {
+        fprintf(stderr, "ERROR: %s\n", lpg_batch_last_error(b));
+        lpg_batch_destroy(b);
+        free(res);
+        return 1;
+    }
+    const double t0 = now();
+    const int rc = dual ? lpg_batch_solve_dual(b, pivots, res) : lpg_batch_solve(b, pivots, rule, res);
+    const double dt = now() - t0;
+    if (rc != 0) {
+        fprintf(stderr, "ERROR: %s\n", lpg_batch_last_error(b));
+        lpg_batch_destroy(b);
+        free(res);
+        return 1;
+    }
+    long long by_status[6] = {0, 0, 0, 0, 0, 0}, total = 0;
+    for (long long q = 0; q < count; q++) {
+        if (res[q].status >= 0 && res[q].status <= 5) by_status[res[q].status]++;
+        total += (long long)res[q].pivots;
+    }
+    lpg_batch_info_t info;
+    lpg_batch_info(b, &info);
+    printf("{\"m\": %lld, \"ncols\": %lld, \"batch\": %lld, \"tier\": \"%s\", \"lds_bytes\": %lld, \"chunk\": %d, "
+           "\"method\": \"%s\", \"rule\": \"%s\", \"statuses\": {",
+           (long long)info.m, (long long)info.ncols, (long long)info.count,
+           info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global", (long long)info.lds_bytes, info.chunk,
+           dual ? "dual" : "primal", rule == LPG_RULE_BLAND && !dual ? "bland" : "dantzig");
+    for (int s = 1; s <= 5; s++) printf("%s\"%s\": %lld", s > 1 ? ", " : "", status_name(s), by_status[s]);
+    printf("}, \"pivots\": %lld, \"seconds\": %.6f, \"lps_per_s\": %.3f, \"pivots_per_s\": %.3f}\n", total, dt,
+           dt > 0 ? (double)count / dt : 0.0, dt > 0 ? (double)total / dt : 0.0);
+    lpg_batch_destroy(b);
+    free(res);
+    return 0;
+}
+
 static char *read_all(const char *path) {
     FILE *f = fopen(path, "rb");
     if (!f) {
@@ -470,7 +518,7 @@ static int load_tableau_file(lpg_ctx **ctx, const char *path, int device) {
 }
 
 int main(int argc, char **argv) {
-    long long m = 0, n = 0, pivots = (long long)1 << 40;
+    long long m = 0, n = 0, pivots = (long long)1 << 40, batch = -1;
     unsigned long long seed = 20220518ull;
     int kind = LPG_GEN_DENSE, rule = LPG_RULE_DANTZIG, device = 0, gpus = 1, push = 1;
     const char *file = NULL, *lpfile = NULL;
@@ -500,6 +548,8 @@ int main(int argc, char **argv) {
             pivots = atoll(argv[++a]);
         } else if (!strcmp(argv[a], "--device") && a + 1 < argc) {
             device = atoi(argv[++a]);
+        } else if (!strcmp(argv[a], "--batch") && a + 1 < argc) {
+            batch = atoll(argv[++a]);
         } else if (!strcmp(argv[a], "--gpus") && a + 1 < argc) {
             gpus = atoi(argv[++a]);
         } else if (!strcmp(argv[a], "--exchange") && a + 1 < argc) {
@@ -510,6 +560,10 @@ int main(int argc, char **argv) {
     }
     if (dual && (bigm || kind == LPG_GEN_ARTIFICIAL)) return usage(argv[0]);
     if (lpfile) return run_lp(lpfile, dump, dual ? LPF_DUAL : bigm ? LPF_BIG_M : LPF_TWO_PHASE, rule, device);
+    if (batch >= 0) {
+        if (!(m > 0 && n > 0) || file || gpus > 1 || kind == LPG_GEN_ARTIFICIAL) return usage(argv[0]);
+        return run_batch(m, n, batch, seed, kind, dual, rule, pivots, device);
+    }
     if (gpus > 1) {
         if (!(m > 0 && n > 0) || gpus > m || gpus > 64) return usage(argv[0]);
         const dist_args da = {m, n, pivots, seed, kind, rule, device, gpus, push, dual};

@@ -307,6 +307,87 @@ int  lpg_set_timing(lpg_ctx *ctx, int enable);
 int  lpg_get_timing(lpg_ctx *ctx, lpg_timing *out);          /* syncs; resets the sums */
 int  lpg_device_sync(lpg_ctx *ctx);
 
+/* ---- batches: many small LPs of one shape in one launch ----
+ * An lpg_ctx spreads ONE tableau over the chip; a caller with a thousand
+ * small LPs (parameter sweeps, scenario sets, the node LPs of a
+ * branch-and-bound tree, SURVEY.md:72) would loop create / solve / destroy.
+ * An lpg_batch holds `count` tableaus of one shape, each (m+1) x ncols as
+ * above (one objective row), back to back in device memory with row pitch
+ * lpg_batch_info_t.ld, and solves them in one launch: one workgroup per LP
+ * (lpg_batch.hip k_batch_solve), no communication between workgroups, the
+ * chip filled by the batch. Each LP has its own basis, status, pivot count,
+ * last (entering, leaving) and pivot log, and computes bit for bit what
+ * lpg_solve / lpg_solve_dual (and oracle/lpo.c) compute for it alone.
+ *
+ * Tier: where a whole tableau plus its pivot row, pivot column and basis fit
+ * the 150 KiB dynamic LDS cap, the tableau stays in LDS while its LP runs
+ * (LPG_BATCH_TIER_LDS); else it stays in device memory and only the pivot
+ * row and column are staged in LDS (LPG_BATCH_TIER_GLOBAL; m + 1 <= 8192 and
+ * ncols <= 8192 -- larger tableaus belong to lpg_create). Env
+ * LPG_BATCH_TIER=global forces the second tier.
+ *
+ * Bounded launches: a launch applies at most lpg_batch_info_t.chunk pivots
+ * per LP (default 4096, fewer for large global-tier tableaus; env
+ * LPG_BATCH_CHUNK); the host relaunches until no LP is still running. A
+ * cycling LP therefore ends at its budget (LPG_ITER_LIMIT), never in an
+ * unbounded kernel.
+ *
+ * Not supported: two-phase / Big-M batches and mixed shapes (pad with zero
+ * rows or columns, which never pivot); LPG_FLAG_NO_LOG is the only flag.
+ * Every argument is validated on the host before any launch. One batch per
+ * host thread; not reentrant. */
+#define LPG_BATCH_TIER_LDS    0
+#define LPG_BATCH_TIER_GLOBAL 1
+#define LPG_BATCH_MAX_DIM     8192   /* m + 1 and ncols of a batch */
+
+typedef struct lpg_batch lpg_batch;
+
+typedef struct {
+    int64_t count, m, ncols, ld;  /* LPs, constraint rows, N+1 columns, device row pitch (doubles) */
+    int32_t tier;                 /* LPG_BATCH_TIER_* */
+    int32_t chunk;                /* pivots per LP and launch */
+    int64_t lds_bytes;            /* dynamic LDS of one workgroup */
+    int64_t log_capacity;         /* pivots recorded per LP (0 with LPG_FLAG_NO_LOG) */
+} lpg_batch_info_t;
+
+/* count >= 1 LPs of m constraint rows and ncols = N+1 columns; flags: 0 or
+ * LPG_FLAG_NO_LOG (anything else: LPG_ERR_ARG). All tableaus start as zeros
+ * with status LPG_RUNNING; load or generate them next. */
+int  lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags);
+void lpg_batch_destroy(lpg_batch *b);                        /* NULL is a no-op */
+const char *lpg_batch_last_error(const lpg_batch *b);        /* NULL: this thread's last create error */
+int  lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *out);
+/* LPs [first, first + n): tableaus = n x (m+1) rows [b | a_1..a_N] of pitch
+ * ld >= ncols, objective row last; basis = n x m 1-based basic columns
+ * (validated: 1..N), or NULL to keep the current ones. The LPs loaded start
+ * again: status LPG_RUNNING, no pivots, empty log. */
+int  lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, int64_t ld,
+                    const int64_t *basis);
+/* LP i = lpg_generate(n_struct, seed + i, kind) for every LP of the batch
+ * (ncols == n_struct + m + 1); kind: LPG_GEN_DENSE, LPG_GEN_DEGENERATE or
+ * LPG_GEN_DUAL. */
+int  lpg_batch_generate(lpg_batch *b, int64_t n_struct, uint64_t seed, int kind);
+int  lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt);
+int  lpg_batch_set_active_columns(lpg_batch *b, int64_t nact);   /* price columns 1..nact of every LP */
+/* Log capacity per LP (default 2 * (m + ncols)), before the first pivot
+ * (LPG_ERR_STATE afterwards). Pivots beyond it are applied and counted but
+ * not recorded. */
+int  lpg_batch_reserve_log(lpg_batch *b, int64_t npivots);
+/* Up to max_pivots MORE pivots per LP, as lpg_solve; out[count] (may be
+ * NULL). A finished LP keeps its status in later calls; an LP whose budget
+ * runs out on its last pivot still reports LPG_OPTIMAL. */
+int  lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out);
+/* The dual simplex with lpg_solve_dual's rules. Every LP must be dual
+ * feasible: else LPG_ERR_STATE, the message names the first offending LP
+ * and nothing has pivoted. */
+int  lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out);
+/* n x (m+1) rows of pitch ld >= ncols / n x m basis entries of LPs [first, first + n) */
+int  lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld);
+int  lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis);
+/* LP lp's log: copies min(recorded, max) pivots, returns the number recorded
+ * (= min(pivots, log capacity)), < 0 on error. */
+int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int64_t max);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ FLAG_NO_SKIP = 0x2
 FLAG_BIG_M = 0x4
 FLAG_EAGER = 0x8
 DEFER_MAX = 128
+BATCH_TIER_LDS, BATCH_TIER_GLOBAL = 0, 1
+BATCH_MAX_DIM = 8192
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -49,6 +51,13 @@ class Info(ctypes.Structure):
 class Timing(ctypes.Structure):
     _fields_ = [("update_ms", ctypes.c_double), ("select_ms", ctypes.c_double),
                 ("comm_ms", ctypes.c_double), ("update_count", ctypes.c_int64), ("update_bytes", ctypes.c_double)]
+
+
+class BatchInfo(ctypes.Structure):
+    """lpg_batch_info_t."""
+    _fields_ = [("count", ctypes.c_int64), ("m", ctypes.c_int64), ("ncols", ctypes.c_int64), ("ld", ctypes.c_int64),
+                ("tier", ctypes.c_int32), ("chunk", ctypes.c_int32), ("lds_bytes", ctypes.c_int64),
+                ("log_capacity", ctypes.c_int64)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -101,6 +110,22 @@ PROTOTYPES = [
     ("lpg_get_timing", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Timing)]),
     ("lpg_device_sync", ctypes.c_int, [ctypes.c_void_p]),
     ("lpg_build_stamp", ctypes.c_char_p, []),
+    ("lpg_batch_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_uint32]),
+    ("lpg_batch_destroy", None, [ctypes.c_void_p]),
+    ("lpg_batch_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("lpg_batch_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BatchInfo)]),
+    ("lpg_batch_load", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64,
+                                      c_int64_p]),
+    ("lpg_batch_generate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int]),
+    ("lpg_batch_set_tolerances", ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double]),
+    ("lpg_batch_set_active_columns", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    ("lpg_batch_reserve_log", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    ("lpg_batch_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
+    ("lpg_batch_solve_dual", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Result)]),
+    ("lpg_batch_get_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64]),
+    ("lpg_batch_get_basis", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p]),
+    ("lpg_batch_get_log", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p, ctypes.c_int64]),
 ]
 
 

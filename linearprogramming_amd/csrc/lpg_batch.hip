@@ -1,0 +1,737 @@
+// lpg_batch.hip — many small LPs of one shape in one launch: one workgroup
+// per LP (include/lpg.h, "batches").
+//
+// The context of lpg_ctx.hip spreads one tableau over the chip and pays a
+// launch-sized cost per pivot whatever the tableau size. Here the chip is
+// filled by the batch instead: workgroup b owns LP b for the whole launch,
+// there is no protocol between workgroups (so no residency requirement: the
+// hardware scheduler balances LPs of different pivot counts), and per pivot
+// the workgroup does what oracle/lpo.c's lpo_solve / lpo_solve_dual do, with
+// the same arithmetic (built with -ffp-contract=off, every fma explicit):
+//   pricing (block argmin) -> ratio test (block argmin)
+//   P[j] = T[r][j] / T[r][k],  C[i] = T[i][k]               (LDS buffers)
+//   T[i][j] = fma(-C[i], P[j], T[i][j])  for i != r,  T[r] = P,  basis[r] = k
+// so every LP is bitwise the oracle's, whatever else is in the batch.
+//
+// TIER_LDS: the whole tableau sits in dynamic LDS for the launch (row pitch
+// odd in doubles: the ratio test's column read, lane = row, then touches 32
+// different 8-byte bank pairs per 32-lane group; row-wise work, lane =
+// column, is conflict-free at any pitch). TIER_GLOBAL: the tableau stays in
+// device memory (one LP's working set is L2-sized), only P and C in LDS.
+//
+// Bounded launches: a launch applies at most `chunk` pivots per LP and the
+// state round-trips through device memory; the host relaunches while the
+// device counter of still-running LPs is non-zero. A workgroup whose LP is
+// finished exits at once.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+#include "../../include/lpg.h"
+#include "lpg_internal.h"
+#include "lpg_device.h"
+
+namespace lpg {
+
+constexpr int kBatchMaxLds = 150 * 1024;   // dynamic LDS cap, as lpg_block.hip's kMaxLds
+constexpr int kBatchChunk = 4096;          // default pivots per LP and launch
+constexpr int MODE_DUAL = 2;               // k_batch_solve's MODE: RULE_DANTZIG, RULE_BLAND or this
+constexpr int TIER_LDS = LPG_BATCH_TIER_LDS, TIER_GLOBAL = LPG_BATCH_TIER_GLOBAL;
+
+struct BatchLP {              // 64 B of state per LP
+    int32_t status;           // of the current solve call (ITER_LIMIT once its budget is spent)
+    int32_t pstatus;          // the primal loop's sticky status (lpo_ctx.status): RUNNING or final
+    int64_t pivots;
+    int64_t last_k, last_r;
+    int64_t budget;           // pivots the current solve call may still apply
+    double  objective;        // T[m][0] after the last launch
+    int64_t pad[2];
+};
+
+struct BatchGeo {
+    double  *T;               // count x (m + 1) x ld
+    int64_t *basis;           // count x m
+    BatchLP *lp;              // count
+    int32_t *logk, *logr;     // count x logcap, or null
+    int32_t *running;         // LPs still RUNNING after this launch
+    int64_t  ld, m, ncols, nact, logcap;
+    double   eps_piv, eps_opt;
+    int32_t  chunk;
+    int32_t  pitch;           // TIER_LDS: row pitch in LDS (doubles, odd)
+    int32_t  txs;             // update tile: 1 << txs lanes along a row, 256 >> txs rows at a time
+};
+
+// ------------------------------------------------------------------------
+// generator: LP b = lpo_generate(n, seed + b, kind), one block per row
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_batch_generate(BatchGeo g, int64_t n, uint64_t seed, int kind) {
+    const int64_t rows = g.m + 1;
+    const int64_t b = (int64_t)blockIdx.x / rows, i = (int64_t)blockIdx.x % rows;
+    const uint64_t s = seed + (uint64_t)b;
+    const uint64_t kA = splitmix64(s ^ (1 * 0xD1B54A32D192ED03ull)), kB = splitmix64(s ^ (2 * 0xD1B54A32D192ED03ull)),
+                   kC = splitmix64(s ^ (3 * 0xD1B54A32D192ED03ull));
+    double *row = g.T + (b * rows + i) * g.ld;
+    const double bscale = (double)n / 8.0;
+    for (int64_t j = threadIdx.x; j < g.ld; j += kBlock) {
+        double x = 0.0;
+        if (i < g.m) {
+            if (j == 0) {
+                if (kind == 0 || kind == 3 || (i & 1)) x = bscale * (1.0 + uniform01(kB, (uint64_t)i));
+                if (kind == 3) x = -x;
+            } else if (j <= n) {
+                const int64_t jj = j - 1;
+                if (kind == 0 || kind == 3) {
+                    x = uniform01(kA, (uint64_t)(i * n + jj));
+                    if (kind == 3) x = -x;
+                } else {
+                    if (jj < i) x = uniform01(kA, (uint64_t)(i * n + jj)) / (double)(i + 1);
+                    else if (jj == i) x = 1.0;
+                }
+            } else if (j == unit_column(g.m, n, i, kind)) {
+                x = 1.0;
+            }
+        } else if (j >= 1 && j <= n) {                 // objective row
+            x = 1.0 + uniform01(kC, (uint64_t)(j - 1));
+            if (kind != 3) x = -x;                     // kind 3: max -c.x, d_j = +c_j (dual feasible)
+        }
+        row[j] = x;
+    }
+    if (i < g.m && threadIdx.x == 0) g.basis[b * g.m + i] = unit_column(g.m, n, i, kind);
+}
+
+// LPs [first, first + n) start again
+__global__ void k_batch_reset(BatchLP *lp, int64_t first, int64_t n) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= n) return;
+    BatchLP z{};
+    z.last_k = z.last_r = -1;
+    lp[first + q] = z;
+}
+
+// a solve call begins: the budget, and the status the oracle's loop would
+// start from (primal: its sticky status; dual: derived anew every call)
+__global__ void k_batch_begin(BatchLP *lp, int64_t count, int64_t budget, int dual) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= count) return;
+    lp[q].budget = budget;
+    lp[q].status = dual ? RUNNING : lp[q].pstatus;
+}
+
+// dual feasibility of every LP: bad[0] = the first LP with a d_j < -eps_opt
+__global__ __launch_bounds__(kBlock) void k_batch_dual_check(BatchGeo g, unsigned long long *bad) {
+    const int64_t b = blockIdx.x;
+    const double *obj = g.T + (b * (g.m + 1) + g.m) * g.ld;
+    bool any = false;
+    for (int64_t j = 1 + threadIdx.x; j <= g.nact; j += kBlock) any |= obj[j] < -g.eps_opt;
+    if (any) atomicMin(bad, (unsigned long long)b);
+}
+
+// ------------------------------------------------------------------------
+// the pivot loop of one LP
+// ------------------------------------------------------------------------
+template <int MODE, int TIER>
+__global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
+    extern __shared__ double smem[];
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    BatchLP *lp = g.lp + b;
+    if (lp->status != RUNNING) return;            // finished in an earlier launch (or call): uniform
+    const int64_t m = g.m, rows = m + 1, ncols = g.ncols;
+    double *gT = g.T + b * rows * g.ld;
+    int64_t *gB = g.basis + b * m;
+    // LDS: [tableau (TIER_LDS)] P[ncols] C[rows] [basis as int32 (TIER_LDS)]
+    const int64_t tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
+    double *T = TIER == TIER_LDS ? smem : gT;
+    double *sP = TIER == TIER_LDS ? smem + rows * tp : smem;
+    double *sC = sP + ncols;
+    int32_t *sB = (int32_t *)(sC + rows);
+    const int tx = 1 << g.txs, ty = kBlock >> g.txs;
+    const int j0 = tid & (tx - 1), i0 = tid >> g.txs;
+
+    const int64_t pivots0 = lp->pivots, budget = lp->budget;
+    int64_t last_k = lp->last_k, last_r = lp->last_r;
+    const int64_t nmax = budget < (int64_t)g.chunk ? budget : (int64_t)g.chunk;
+    if (TIER == TIER_LDS) {
+        for (int64_t i = i0; i < rows; i += ty)
+            for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * g.ld + j];
+        for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
+    }
+    __syncthreads();
+
+    int32_t status = RUNNING;
+    int64_t done = 0;
+    for (;;) {
+        int64_t k, r;
+        double piv;
+        if constexpr (MODE != MODE_DUAL) {
+            // pricing (lpo.c price): also the final peek when the budget is spent
+            PricePart pb{0.0, -1, 0, 0};
+            for (int64_t j = 1 + tid; j <= g.nact; j += kBlock) {
+                const double d = T[m * tp + j];
+                PricePart c{d, d < -g.eps_opt ? j : -1, 0, (int32_t)j};
+                pp_take(pb, c, pp_better<MODE>(c, pb));
+            }
+            pb = block_argmin_pp<MODE>(pb);
+            k = pb.j;
+            if (k < 0) {
+                status = OPTIMAL;
+                break;
+            }
+            if (done == nmax) {
+                if (done == budget) status = ITER_LIMIT;
+                break;
+            }
+            // ratio test (lpo.c ratio_block, cand_less)
+            Cand cb{0.0, 0.0, 0, -1};
+            for (int64_t i = tid; i < m; i += kBlock) {
+                const double a = T[i * tp + k], bi = T[i * tp];
+                Cand c;
+                c.theta = bi > 0.0 ? bi / a : 0.0;
+                c.piv = a;
+                c.key = MODE == RULE_BLAND ? (TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]) : i;
+                c.row = a > g.eps_piv ? i : -1;
+                cand_take(cb, c, cand_better(c, cb));
+            }
+            cb = block_argmin_cand(cb);
+            r = cb.row;
+            if (r < 0) {
+                status = UNBOUNDED;
+                break;
+            }
+            piv = cb.piv;
+            if (!isfinite(piv) || !isfinite(T[r * tp])) {
+                status = NUMERIC;
+                break;
+            }
+        } else {
+            // leaving row (lpo_solve_dual): most negative b_i, ties -> smallest row
+            PricePart pb{0.0, -1, 0, 0};
+            for (int64_t i = tid; i < m; i += kBlock) {
+                const double bi = T[i * tp];
+                PricePart c{bi, bi < -g.eps_opt ? i : -1, 0, (int32_t)i};
+                pp_take(pb, c, pp_better<RULE_DANTZIG>(c, pb));
+            }
+            pb = block_argmin_pp<RULE_DANTZIG>(pb);
+            r = pb.j;
+            if (r < 0) {
+                status = OPTIMAL;
+                break;
+            }
+            if (done == nmax) {
+                if (done == budget) status = ITER_LIMIT;
+                break;
+            }
+            // entering column: min d_j / -a_rj over a_rj < -eps_piv, ties -> smallest j
+            Cand cb{0.0, 0.0, 0, -1};
+            for (int64_t j = 1 + tid; j <= g.nact; j += kBlock) {
+                const double a = T[r * tp + j], d = T[m * tp + j];
+                Cand c;
+                c.theta = d > 0.0 ? d / -a : 0.0;
+                c.piv = a;
+                c.key = j;
+                c.row = a < -g.eps_piv ? j : -1;
+                cand_take(cb, c, cand_better(c, cb));
+            }
+            cb = block_argmin_cand(cb);
+            k = cb.row;
+            if (k < 0) {
+                status = INFEASIBLE;
+                break;
+            }
+            piv = cb.piv;
+        }
+        // P, C
+        for (int64_t j = tid; j < ncols; j += kBlock) sP[j] = T[r * tp + j] / piv;
+        for (int64_t i = tid; i < rows; i += kBlock) sC[i] = T[i * tp + k];
+        __syncthreads();
+        // rank-1 update (lpo_pivot)
+        // a thread keeps its column's P[j] and walks the rows four at a time:
+        // the four loads are issued before the first store, so their latencies
+        // overlap (the compiler cannot reorder them itself: T, P and C may alias)
+        for (int64_t j = j0; j < ncols; j += tx) {
+            const double pj = sP[j];
+            double *col = T + j;
+            int64_t i = i0;
+            for (; i + 3 * ty < rows; i += 4 * ty) {
+                double c[4], t[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    c[u] = sC[i + u * ty];
+                    t[u] = col[(i + u * ty) * tp];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) col[(i + u * ty) * tp] = (i + u * ty == r) ? pj : fma(-c[u], pj, t[u]);
+            }
+            for (; i < rows; i += ty) col[i * tp] = (i == r) ? pj : fma(-sC[i], pj, col[i * tp]);
+        }
+        if (tid == 0) {
+            gB[r] = k;
+            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
+            const int64_t q = pivots0 + done;
+            if (g.logk && q < g.logcap) {
+                g.logk[b * g.logcap + q] = (int32_t)k;
+                g.logr[b * g.logcap + q] = (int32_t)r;
+            }
+        }
+        last_k = k;
+        last_r = r;
+        done++;
+        __syncthreads();
+    }
+
+    // store the state
+    if (TIER == TIER_LDS && done > 0) {
+        for (int64_t i = i0; i < rows; i += ty)
+            for (int64_t j = j0; j < ncols; j += tx) gT[i * g.ld + j] = T[i * tp + j];
+    }
+    if (tid == 0) {
+        lp->status = status;
+        if (MODE != MODE_DUAL && status != RUNNING && status != ITER_LIMIT) lp->pstatus = status;
+        lp->pivots = pivots0 + done;
+        lp->last_k = last_k;
+        lp->last_r = last_r;
+        lp->budget = budget - done;
+        lp->objective = T[m * tp];
+        if (status == RUNNING) atomicAdd(g.running, 1);
+    }
+}
+
+}  // namespace lpg
+
+// ---------------------------------------------------------------------------
+// host: the batch object and the extern "C" entry points
+// ---------------------------------------------------------------------------
+using namespace lpg;
+
+struct lpg_batch {
+    int device = 0;
+    int64_t count = 0, m = 0, ncols = 0, ld = 0, nact = 0;
+    uint32_t flags = 0;
+    double eps_piv = 1e-9, eps_opt = 1e-9;
+    int tier = TIER_LDS;
+    int64_t lds = 0;
+    int chunk = kBatchChunk;
+    int pitch = 0, txs = 0;
+    int64_t logcap = 0;
+    bool pivoted = false;         // a solve call has run since the last load / generate of the whole batch
+    double *T = nullptr;
+    int64_t *basis = nullptr;
+    BatchLP *lp = nullptr;
+    int32_t *logk = nullptr, *logr = nullptr;
+    int32_t *running = nullptr;
+    unsigned long long *bad = nullptr;
+    hipStream_t stream = nullptr;
+    char err[512] = {0};
+};
+
+namespace {
+
+thread_local char g_berr[512];
+
+int bfail(lpg_batch *b, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b) snprintf(b->err, sizeof b->err, "%s", buf);
+    snprintf(g_berr, sizeof g_berr, "%s", buf);
+    return code;
+}
+
+#define BHIPCHK(b, x)                                                                 \
+    do {                                                                              \
+        hipError_t e_ = (x);                                                          \
+        if (e_ != hipSuccess) {                                                       \
+            (void)hipGetLastError();                                                  \
+            return bfail((b), LPG_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));   \
+        }                                                                             \
+    } while (0)
+
+BatchGeo bgeo(const lpg_batch *b) {
+    BatchGeo g{};
+    g.T = b->T;
+    g.basis = b->basis;
+    g.lp = b->lp;
+    g.logk = b->logk;
+    g.logr = b->logr;
+    g.running = b->running;
+    g.ld = b->ld;
+    g.m = b->m;
+    g.ncols = b->ncols;
+    g.nact = b->nact;
+    g.logcap = b->logcap;
+    g.eps_piv = b->eps_piv;
+    g.eps_opt = b->eps_opt;
+    g.chunk = b->chunk;
+    g.pitch = b->pitch;
+    g.txs = b->txs;
+    return g;
+}
+
+// dynamic LDS of one workgroup: [tableau at an odd pitch] P C [int32 basis]
+int64_t lds_bytes(int tier, int64_t m, int64_t ncols) {
+    const int64_t rows = m + 1, pitch = ncols | 1;
+    int64_t d = ncols + rows;
+    if (tier == TIER_LDS) d += rows * pitch + (m + 1) / 2;
+    return d * (int64_t)sizeof(double);
+}
+
+unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+int range_ok(lpg_batch *b, const char *what, int64_t first, int64_t n) {
+    if (first < 0 || n < 0 || first > b->count || n > b->count - first)
+        return bfail(b, LPG_ERR_ARG, "%s: LPs [%lld, %lld) outside the batch of %lld", what, (long long)first,
+                     (long long)(first + n), (long long)b->count);
+    return 0;
+}
+
+int alloc_log(lpg_batch *b, int64_t cap) {
+    if (b->logk) (void)hipFree(b->logk);
+    if (b->logr) (void)hipFree(b->logr);
+    b->logk = b->logr = nullptr;
+    b->logcap = 0;
+    if ((b->flags & LPG_FLAG_NO_LOG) || cap == 0) return 0;
+    const size_t bytes = (size_t)b->count * (size_t)cap * sizeof(int32_t);
+    if (hipMalloc(&b->logk, bytes) != hipSuccess || hipMalloc(&b->logr, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (b->logk) (void)hipFree(b->logk);
+        b->logk = b->logr = nullptr;
+        return bfail(b, LPG_ERR_OOM, "hipMalloc(pivot log, 2 x %zu bytes) failed", bytes);
+    }
+    b->logcap = cap;
+    return 0;
+}
+
+template <int MODE, int TIER>
+int launch_solve_t(lpg_batch *b) {
+    static std::atomic<unsigned long long> attr{0};
+    const int dev = b->device & 63;
+    if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
+        if (hipFuncSetAttribute((const void *)k_batch_solve<MODE, TIER>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kBatchMaxLds) != hipSuccess) {
+            (void)hipGetLastError();
+            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(k_batch_solve, %d bytes of LDS) failed", kBatchMaxLds);
+        }
+        attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
+    }
+    hipLaunchKernelGGL((k_batch_solve<MODE, TIER>), dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream,
+                       bgeo(b));
+    return 0;
+}
+
+int launch_solve(lpg_batch *b, int mode) {
+    const bool l = b->tier == TIER_LDS;
+    switch (mode) {
+    case RULE_DANTZIG: return l ? launch_solve_t<RULE_DANTZIG, TIER_LDS>(b) : launch_solve_t<RULE_DANTZIG, TIER_GLOBAL>(b);
+    case RULE_BLAND: return l ? launch_solve_t<RULE_BLAND, TIER_LDS>(b) : launch_solve_t<RULE_BLAND, TIER_GLOBAL>(b);
+    default: return l ? launch_solve_t<MODE_DUAL, TIER_LDS>(b) : launch_solve_t<MODE_DUAL, TIER_GLOBAL>(b);
+    }
+}
+
+int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "max_pivots < 0");
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (mode == MODE_DUAL) {
+        const unsigned long long none = ~0ull;
+        unsigned long long bad = none;
+        BHIPCHK(b, hipMemcpyAsync(b->bad, &none, sizeof none, hipMemcpyHostToDevice, b->stream));
+        hipLaunchKernelGGL(k_batch_dual_check, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b), b->bad);
+        BHIPCHK(b, hipGetLastError());
+        BHIPCHK(b, hipMemcpyAsync(&bad, b->bad, sizeof bad, hipMemcpyDeviceToHost, b->stream));
+        BHIPCHK(b, hipStreamSynchronize(b->stream));
+        if (bad != none)
+            return bfail(b, LPG_ERR_STATE, "lpg_batch_solve_dual: LP %llu is not dual feasible (a d_j < -eps_opt); "
+                                           "nothing has pivoted", bad);
+    }
+    hipLaunchKernelGGL(k_batch_begin, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, b->count,
+                       max_pivots, mode == MODE_DUAL ? 1 : 0);
+    BHIPCHK(b, hipGetLastError());
+    b->pivoted = true;
+    // every launch spends `chunk` of each running LP's budget (or ends the LP)
+    const int64_t max_launches = max_pivots / b->chunk + 2;
+    for (int64_t it = 0;; it++) {
+        int32_t running = 0;
+        BHIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
+        if (int rc = launch_solve(b, mode)) return rc;
+        BHIPCHK(b, hipGetLastError());
+        BHIPCHK(b, hipMemcpyAsync(&running, b->running, sizeof running, hipMemcpyDeviceToHost, b->stream));
+        BHIPCHK(b, hipStreamSynchronize(b->stream));
+        if (running == 0) break;
+        if (it + 1 >= max_launches)
+            return bfail(b, LPG_ERR_DEVICE, "lpg_batch: %d LPs still running after %lld launches of %d pivots", running,
+                         (long long)(it + 1), b->chunk);
+    }
+    if (out) {
+        std::vector<BatchLP> h((size_t)b->count);
+        BHIPCHK(b, hipMemcpy(h.data(), b->lp, h.size() * sizeof(BatchLP), hipMemcpyDeviceToHost));
+        for (int64_t q = 0; q < b->count; q++) {
+            out[q].status = h[q].status;
+            out[q].rule = mode == RULE_BLAND ? LPG_RULE_BLAND : LPG_RULE_DANTZIG;
+            out[q].pivots = h[q].pivots;
+            out[q].objective = h[q].objective;
+            out[q].entering = h[q].last_k;
+            out[q].leaving = h[q].last_r;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *lpg_batch_last_error(const lpg_batch *b) { return b ? b->err : g_berr; }
+
+int lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags) {
+    if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (count < 1 || m < 1 || ncols < 2)
+        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: bad shape count=%lld m=%lld ncols=%lld (need count >= 1, "
+                                           "m >= 1, ncols >= 2)", (long long)count, (long long)m, (long long)ncols);
+    if (flags & ~(uint32_t)LPG_FLAG_NO_LOG)
+        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: flags 0x%x not supported (LPG_FLAG_NO_LOG only: no Big-M, "
+                                           "eager or no-skip batches)", flags);
+    if (m + 1 > LPG_BATCH_MAX_DIM || ncols > LPG_BATCH_MAX_DIM)
+        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: m + 1 = %lld, ncols = %lld exceed %d; a tableau this large "
+                                           "belongs to lpg_create", (long long)(m + 1), (long long)ncols, LPG_BATCH_MAX_DIM);
+    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: device %d", device);
+    const int64_t rows = m + 1, ld = (ncols + 63) & ~(int64_t)63;   // the engine's padded pitch (512-byte rows)
+    if (count > (int64_t)0x7fffffff / rows)
+        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: count * (m + 1) = %lld x %lld exceeds 2^31 - 1",
+                     (long long)count, (long long)rows);
+    int chunk = 0;
+    if (const char *ce = getenv("LPG_BATCH_CHUNK")) {
+        const long long v = atoll(ce);
+        if (v < 1 || v > (1 << 20))
+            return bfail(nullptr, LPG_ERR_ARG, "LPG_BATCH_CHUNK=%s out of range [1, %d]", ce, 1 << 20);
+        chunk = (int)v;
+    }
+    lpg_batch *b = new lpg_batch();
+    b->device = device;
+    b->count = count;
+    b->m = m;
+    b->ncols = ncols;
+    b->ld = ld;
+    b->nact = ncols - 1;
+    b->flags = flags;
+    const char *te = getenv("LPG_BATCH_TIER");
+    const bool force_global = te && !strcmp(te, "global");
+    b->tier = (!force_global && lds_bytes(TIER_LDS, m, ncols) <= kBatchMaxLds) ? TIER_LDS : TIER_GLOBAL;
+    b->lds = lds_bytes(b->tier, m, ncols);
+    b->pitch = (int)(ncols | 1);
+    while ((1 << b->txs) < ncols && b->txs < 8) b->txs++;
+    if (!chunk) {
+        // a launch stays bounded in time as well as in pivots: the LDS tier
+        // spends microseconds per pivot; a global-tier workgroup streams its
+        // tableau twice per pivot at some tens of GB/s, so large tableaus get
+        // fewer pivots per launch (about 0.1 s at 50 GB/s)
+        chunk = kBatchChunk;
+        if (b->tier == TIER_GLOBAL) {
+            const double per_pivot = 16.0 * (double)rows * (double)ncols / 50e9;
+            chunk = (int)std::min<double>(kBatchChunk, std::max(16.0, 0.1 / per_pivot));
+        }
+    }
+    b->chunk = chunk;
+    auto die = [&](int code) {
+        snprintf(g_berr, sizeof g_berr, "%s", b->err);
+        lpg_batch_destroy(b);
+        return code;
+    };
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    const size_t tbytes = (size_t)count * (size_t)rows * (size_t)ld * sizeof(double);
+    if (hipMalloc(&b->T, tbytes) != hipSuccess || hipMalloc(&b->basis, (size_t)count * (size_t)m * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc(&b->lp, (size_t)count * sizeof(BatchLP)) != hipSuccess ||
+        hipMalloc(&b->running, sizeof(int32_t)) != hipSuccess || hipMalloc(&b->bad, sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_OOM, "hipMalloc(batch of %lld tableaus, %zu bytes) failed", (long long)count, tbytes);
+        return die(LPG_ERR_OOM);
+    }
+    if (int rc = alloc_log(b, 2 * (m + ncols))) return die(rc);
+    if ((e = hipStreamCreate(&b->stream)) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    // zero tableaus (the padding columns stay zero for good), slack-less bases, fresh states
+    if (hipMemsetAsync(b->T, 0, tbytes, b->stream) != hipSuccess ||
+        hipMemsetAsync(b->basis, 0, (size_t)count * (size_t)m * sizeof(int64_t), b->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipMemset failed");
+        return die(LPG_ERR_DEVICE);
+    }
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, count);
+    if ((e = hipStreamSynchronize(b->stream)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) {
+        bfail(b, LPG_ERR_DEVICE, "batch setup: %s", hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    *out = b;
+    return 0;
+}
+
+void lpg_batch_destroy(lpg_batch *b) {
+    if (!b) return;
+    if (b->T || b->stream) (void)hipSetDevice(b->device);
+    if (b->stream) {
+        (void)hipStreamSynchronize(b->stream);
+        (void)hipStreamDestroy(b->stream);
+    }
+    if (b->T) (void)hipFree(b->T);
+    if (b->basis) (void)hipFree(b->basis);
+    if (b->lp) (void)hipFree(b->lp);
+    if (b->logk) (void)hipFree(b->logk);
+    if (b->logr) (void)hipFree(b->logr);
+    if (b->running) (void)hipFree(b->running);
+    if (b->bad) (void)hipFree(b->bad);
+    delete b;
+}
+
+int lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *o) {
+    if (!b || !o) return bfail(const_cast<lpg_batch *>(b), LPG_ERR_ARG, "NULL argument");
+    o->count = b->count;
+    o->m = b->m;
+    o->ncols = b->ncols;
+    o->ld = b->ld;
+    o->tier = b->tier;
+    o->chunk = b->chunk;
+    o->lds_bytes = b->lds;
+    o->log_capacity = b->logcap;
+    return 0;
+}
+
+int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, int64_t ld, const int64_t *basis) {
+    if (!b || !tableaus) return bfail(b, LPG_ERR_ARG, "lpg_batch_load: NULL argument");
+    if (int rc = range_ok(b, "lpg_batch_load", first, n)) return rc;
+    if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_load: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
+    if (basis)
+        for (int64_t q = 0; q < n * b->m; q++)
+            if (basis[q] < 1 || basis[q] >= b->ncols)
+                return bfail(b, LPG_ERR_ARG, "lpg_batch_load: basis[%lld] of LP %lld out of range 1..%lld",
+                             (long long)(q % b->m), (long long)(first + q / b->m), (long long)(b->ncols - 1));
+    if (n == 0) return 0;
+    BHIPCHK(b, hipSetDevice(b->device));
+    const int64_t rows = b->m + 1;
+    // rows are back to back on both sides: one strided copy of n * (m + 1) rows
+    BHIPCHK(b, hipMemcpy2DAsync(b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double), tableaus,
+                                (size_t)ld * sizeof(double), (size_t)b->ncols * sizeof(double), (size_t)(n * rows),
+                                hipMemcpyHostToDevice, b->stream));
+    if (basis)
+        BHIPCHK(b, hipMemcpyAsync(b->basis + first * b->m, basis, (size_t)(n * b->m) * sizeof(int64_t),
+                                  hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(n)), dim3(kBlock), 0, b->stream, b->lp, first, n);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    if (first == 0 && n == b->count) b->pivoted = false;
+    return 0;
+}
+
+int lpg_batch_generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (n < 1 || b->ncols != n + b->m + 1)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
+                     (long long)(n + b->m + 1));
+    if (kind != LPG_GEN_DENSE && kind != LPG_GEN_DEGENERATE && kind != LPG_GEN_DUAL)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: kind %d (dense, degenerate or dual only)", kind);
+    BHIPCHK(b, hipSetDevice(b->device));
+    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + 1))), dim3(kBlock), 0, b->stream, bgeo(b), n,
+                       seed, kind);
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    b->pivoted = false;
+    return 0;
+}
+
+int lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt) {
+    if (!b || !(eps_piv >= 0) || !(eps_opt >= 0)) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_tolerances: bad tolerances");
+    b->eps_piv = eps_piv;
+    b->eps_opt = eps_opt;
+    return 0;
+}
+
+int lpg_batch_set_active_columns(lpg_batch *b, int64_t nact) {
+    if (!b || nact < 1 || nact > b->ncols - 1)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_set_active_columns: nact out of range 1..N");
+    b->nact = nact;
+    return 0;
+}
+
+int lpg_batch_reserve_log(lpg_batch *b, int64_t npivots) {
+    if (!b || npivots < 0) return bfail(b, LPG_ERR_ARG, "lpg_batch_reserve_log: bad arguments");
+    if (b->pivoted) return bfail(b, LPG_ERR_STATE, "lpg_batch_reserve_log: set the log capacity before the first solve");
+    if (npivots > (int64_t)0x7fffffff || (double)npivots * (double)b->count > 4e9)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_reserve_log: %lld pivots x %lld LPs is too large", (long long)npivots,
+                     (long long)b->count);
+    BHIPCHK(b, hipSetDevice(b->device));
+    return alloc_log(b, npivots);
+}
+
+int lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out) {
+    if (b && rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve: rule %d", rule);
+    return batch_run(b, max_pivots, rule, out);
+}
+
+int lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out) {
+    return batch_run(b, max_pivots, MODE_DUAL, out);
+}
+
+int lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld) {
+    if (!b || !out) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: NULL argument");
+    if (int rc = range_ok(b, "lpg_batch_get_rows", first, n)) return rc;
+    if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
+    if (n == 0) return 0;
+    BHIPCHK(b, hipSetDevice(b->device));
+    const int64_t rows = b->m + 1;
+    BHIPCHK(b, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double),
+                                (size_t)b->ncols * sizeof(double), (size_t)(n * rows), hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis) {
+    if (!b || !basis) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_basis: NULL argument");
+    if (int rc = range_ok(b, "lpg_batch_get_basis", first, n)) return rc;
+    if (n == 0) return 0;
+    BHIPCHK(b, hipSetDevice(b->device));
+    BHIPCHK(b, hipMemcpy(basis, b->basis + first * b->m, (size_t)(n * b->m) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int64_t max) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (lp < 0 || lp >= b->count)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_get_log: LP %lld outside the batch of %lld", (long long)lp, (long long)b->count);
+    if (!b->logk) return 0;
+    BHIPCHK(b, hipSetDevice(b->device));
+    BatchLP h;
+    BHIPCHK(b, hipMemcpy(&h, b->lp + lp, sizeof h, hipMemcpyDeviceToHost));
+    const int64_t rec = std::min(h.pivots, b->logcap);
+    const int64_t n = std::max<int64_t>(0, std::min(rec, max));
+    if (n > 0 && (k || r)) {
+        std::vector<int32_t> t((size_t)n);
+        for (int w = 0; w < 2; w++) {
+            int64_t *dst = w ? r : k;
+            if (!dst) continue;
+            BHIPCHK(b, hipMemcpy(t.data(), (w ? b->logr : b->logk) + lp * b->logcap, (size_t)n * sizeof(int32_t),
+                                 hipMemcpyDeviceToHost));
+            for (int64_t q = 0; q < n; q++) dst[q] = t[(size_t)q];
+        }
+    }
+    return rec;
+}
+
+}  // extern "C"

@@ -13,6 +13,29 @@ namespace lpg {
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------------
+// synthetic generator draws (bitwise identical to oracle lpo_generate)
+// ------------------------------------------------------------------------
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ double uniform01(uint64_t key, uint64_t idx) {
+    return (double)(splitmix64(key ^ (idx * 0x9E3779B97F4A7C15ull)) >> 11) * 0x1.0p-53;
+}
+
+// Column of row i's initial unit column (oracle lpo_unit_column): kinds 0/1
+// slack 1+n+i; kind 2 slacks of even rows first, then the artificials of the
+// odd (equality) rows from art_first = 1+n+ceil(m/2).
+__host__ __device__ __forceinline__ int64_t unit_column(int64_t m, int64_t n, int64_t i, int kind) {
+    if (kind != 2) return 1 + n + i;
+    return (i & 1) ? 1 + n + (m + 1) / 2 + i / 2 : 1 + n + i / 2;
+}
+
+// ------------------------------------------------------------------------
 // reductions: 64-lane wave shuffles, then the 4 waves through LDS
 // ------------------------------------------------------------------------
 

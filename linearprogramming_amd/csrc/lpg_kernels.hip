@@ -27,16 +27,8 @@ namespace lpg {
 // synthetic generator (bitwise identical to oracle lpo_generate)
 // ------------------------------------------------------------------------
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ double uniform01(uint64_t key, uint64_t idx) {
-    return (double)(splitmix64(key ^ (idx * 0x9E3779B97F4A7C15ull)) >> 11) * 0x1.0p-53;
-}
+// (splitmix64, uniform01 and unit_column live in lpg_device.h: the batch
+// generator of lpg_batch.hip draws the same numbers)
 
 static inline uint64_t splitmix64_host(uint64_t x) {
     uint64_t z = x + 0x9E3779B97F4A7C15ull;
@@ -46,14 +38,6 @@ static inline uint64_t splitmix64_host(uint64_t x) {
 }
 static inline uint64_t subkey(uint64_t seed, uint64_t which) {
     return splitmix64_host(seed ^ (which * 0xD1B54A32D192ED03ull));
-}
-
-// Column of row i's initial unit column (oracle lpo_unit_column): kinds 0/1
-// slack 1+n+i; kind 2 slacks of even rows first, then the artificials of the
-// odd (equality) rows from art_first = 1+n+ceil(m/2).
-__host__ __device__ __forceinline__ int64_t unit_column(int64_t m, int64_t n, int64_t i, int kind) {
-    if (kind != 2) return 1 + n + i;
-    return (i & 1) ? 1 + n + (m + 1) / 2 + i / 2 : 1 + n + i / 2;
 }
 
 // grid: x = local row, y = chunk of 512 columns (256 lanes x 2). Every rank

@@ -289,3 +289,106 @@ class Engine:
         t = L.Timing()
         self._check(self.lib.lpg_get_timing(self._ctx, ctypes.byref(t)), "lpg_get_timing")
         return t
+
+
+class BatchEngine:
+    """`count` LPs of one shape, each an (m+1) x ncols tableau, solved in one
+    launch with one workgroup per LP (include/lpg.h, "batches")."""
+
+    def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None):
+        self.lib = lib if lib is not None else L.load()
+        self._b = ctypes.c_void_p()
+        rc = self.lib.lpg_batch_create(ctypes.byref(self._b), device, count, m, ncols, flags)
+        if rc != 0:
+            raise LPGError(f"lpg_batch_create rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+        self.count, self.m, self.ncols = count, m, ncols
+
+    def close(self):
+        if self._b:
+            self.lib.lpg_batch_destroy(self._b)
+            self._b = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_batch_last_error(self._b).decode()}")
+        return rc
+
+    @property
+    def info(self) -> L.BatchInfo:
+        i = L.BatchInfo()
+        self._check(self.lib.lpg_batch_info(self._b, ctypes.byref(i)), "lpg_batch_info")
+        return i
+
+    # -- loading ---------------------------------------------------------
+    def load(self, T: np.ndarray, basis=None, first: int = 0):
+        """T: [n, m+1, ncols] tableaus (objective row last), basis: [n, m]; LPs first .. first + n - 1."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim != 3 or T.shape[1] != self.m + 1 or T.shape[2] != self.ncols:
+            raise LPGError(f"load: tableaus of shape {T.shape}, want [n, {self.m + 1}, {self.ncols}]")
+        bp = None
+        if basis is not None:
+            basis = np.ascontiguousarray(basis, dtype=np.int64)
+            if basis.shape != (T.shape[0], self.m):
+                raise LPGError(f"load: basis of shape {basis.shape}, want [{T.shape[0]}, {self.m}]")
+            bp = basis.ctypes.data_as(L.c_int64_p)
+        self._check(self.lib.lpg_batch_load(self._b, first, T.shape[0], T.ctypes.data_as(L.c_double_p), self.ncols, bp),
+                    "lpg_batch_load")
+
+    def generate(self, n: int, seed: int = 20220518, kind: int = L.GEN_DENSE):
+        """LP b = Engine.generate(n, seed + b, kind)."""
+        self._check(self.lib.lpg_batch_generate(self._b, n, seed, kind), "lpg_batch_generate")
+
+    def set_tolerances(self, eps_piv=1e-9, eps_opt=1e-9):
+        self._check(self.lib.lpg_batch_set_tolerances(self._b, eps_piv, eps_opt), "lpg_batch_set_tolerances")
+
+    def set_active_columns(self, nact: int):
+        self._check(self.lib.lpg_batch_set_active_columns(self._b, nact), "lpg_batch_set_active_columns")
+
+    def reserve_log(self, n: int):
+        self._check(self.lib.lpg_batch_reserve_log(self._b, n), "lpg_batch_reserve_log")
+
+    # -- pivoting --------------------------------------------------------
+    def solve(self, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> list:
+        r = (L.Result * self.count)()
+        self._check(self.lib.lpg_batch_solve(self._b, max_pivots, rule, r), "lpg_batch_solve")
+        return [_res(x) for x in r]
+
+    def solve_dual(self, max_pivots: int = 1 << 40) -> list:
+        r = (L.Result * self.count)()
+        self._check(self.lib.lpg_batch_solve_dual(self._b, max_pivots, r), "lpg_batch_solve_dual")
+        return [_res(x) for x in r]
+
+    # -- readout ---------------------------------------------------------
+    def get_rows(self, first: int = 0, n: int = None) -> np.ndarray:
+        n = self.count - first if n is None else n
+        out = np.zeros((n, self.m + 1, self.ncols), dtype=np.float64)
+        self._check(self.lib.lpg_batch_get_rows(self._b, first, n, out.ctypes.data_as(L.c_double_p), self.ncols),
+                    "lpg_batch_get_rows")
+        return out
+
+    def get_basis(self, first: int = 0, n: int = None) -> np.ndarray:
+        n = self.count - first if n is None else n
+        out = np.zeros((n, self.m), dtype=np.int64)
+        self._check(self.lib.lpg_batch_get_basis(self._b, first, n, out.ctypes.data_as(L.c_int64_p)),
+                    "lpg_batch_get_basis")
+        return out
+
+    def get_log(self, lp: int):
+        n = self._check(self.lib.lpg_batch_get_log(self._b, lp, None, None, 0), "lpg_batch_get_log")
+        k = np.zeros(max(n, 1), dtype=np.int64)
+        r = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self.lib.lpg_batch_get_log(self._b, lp, k.ctypes.data_as(L.c_int64_p),
+                                               r.ctypes.data_as(L.c_int64_p), n), "lpg_batch_get_log")
+        return k[:n], r[:n]

@@ -1,0 +1,149 @@
+"""Batch-solver test plumbing (tests/test_gpu_batch.py, tests/batch_worker.py).
+
+A case is a JSON-able dict ("spec"); run_batch(spec) runs it on the device
+through BatchEngine, run_oracle(spec) runs every LP of it through the CPU
+oracle, one Oracle per LP, and assert_same compares the two bit for bit:
+status, pivot count, objective bits, last (entering, leaving), basis, the
+whole log and the whole (m+1) x ncols tableau. Both return the same dict of
+arrays, so a device run made in a fresh subprocess (another tier, another
+chunk) travels back as an .npz file.
+
+spec keys: m, n, B, kind (generator), seed, rule, budgets (one solve call
+each; default [50 * (m + n)]), dual, construct ("gen": the device generator;
+"mixed", "kat", "dual_infeasible": tableaus built on the host by
+build_tableaus and loaded), reserve_log, nact, eps ([eps_piv, eps_opt]),
+only (solve LP `only` alone in a batch of 1).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+SEED = 20220518
+
+
+def spec(m, n, B=8, kind=0, rule=0, **kw):
+    s = {"m": m, "n": n, "B": B, "kind": kind, "seed": SEED, "rule": rule, "budgets": [50 * (m + n)], "dual": False,
+         "construct": "gen", "reserve_log": None, "nact": None, "eps": None, "only": None}
+    s.update(kw)
+    return s
+
+
+def ncols_of(s):
+    return s["n"] + s["m"] + 1
+
+
+def build_tableaus(s):
+    """(T[B, m+1, ncols], basis[B, m]) of the LPs before any pivot."""
+    from oracle.lpo import Oracle
+    m, n, B = s["m"], s["n"], s["B"]
+    T = np.zeros((B, m + 1, ncols_of(s)))
+    basis = np.zeros((B, m), dtype=np.int64)
+    for b in range(B):
+        o = Oracle(m, ncols_of(s))
+        o.generate(n, s["seed"] + b, s["kind"])
+        T[b], basis[b] = o.get_rows(), o.get_basis()
+        o.close()
+    c = s["construct"]
+    if c == "mixed":
+        # LPs 0..3: structural column 1 + b negated in every constraint row (a ray: UNBOUNDED);
+        # LP 4: a non-negative objective row (OPTIMAL at once); the rest plain
+        for b in range(4):
+            T[b, :m, 1 + b] *= -1.0
+        T[4, m, :] = np.abs(T[4, m, :])
+    elif c == "kat":
+        # LP 1: Source/testdata.txt with `max:` (z* = 12), as __graft_entry__.smoke() loads it
+        assert (m, n) == (2, 2)
+        T[1] = np.array([[51 / 14, 1, 9 / 14, 1, 0], [1 / 3, 2, -1, 0, 1], [0, -1, -1, 0, 0]])
+        basis[1] = [3, 4]
+    elif c == "dual_infeasible":
+        # LP b: row b's structural entries made non-negative: b_b < 0 with no negative entry left
+        for b in range(B):
+            T[b, b, 1:n + 1] = np.abs(T[b, b, 1:n + 1])
+    elif c != "gen":
+        raise ValueError(c)
+    if s["only"] is not None:
+        T, basis = T[s["only"]:s["only"] + 1], basis[s["only"]:s["only"] + 1]
+    return T, basis
+
+
+def _pack(results, rows, basis, logs, calls, logcap):
+    return {
+        "status": np.array([r.status for r in results], dtype=np.int64),
+        "pivots": np.array([r.pivots for r in results], dtype=np.int64),
+        "objective": np.array([r.objective for r in results], dtype=np.float64),
+        "entering": np.array([r.entering for r in results], dtype=np.int64),
+        "leaving": np.array([r.leaving for r in results], dtype=np.int64),
+        "rows": rows, "basis": basis,
+        "loglen": np.array([len(k) for k, _ in logs], dtype=np.int64),
+        "logk": np.concatenate([k for k, _ in logs] + [np.zeros(0, dtype=np.int64)]),
+        "logr": np.concatenate([r for _, r in logs] + [np.zeros(0, dtype=np.int64)]),
+        "calls": np.array(calls, dtype=np.int64),          # [call, LP] -> status after that call
+        "logcap": np.array(logcap, dtype=np.int64),
+    }
+
+
+def run_batch(s):
+    """The case on the device; also returns info.tier / chunk / lds_bytes."""
+    import linearprogramming_amd as lpg
+    B = 1 if s["only"] is not None else s["B"]
+    e = lpg.BatchEngine(B, s["m"], ncols_of(s))
+    try:
+        if s["construct"] == "gen" and s["only"] is None:
+            e.generate(s["n"], s["seed"], s["kind"])
+        else:
+            e.load(*build_tableaus(s))
+        if s["reserve_log"] is not None:
+            e.reserve_log(s["reserve_log"])
+        if s["nact"] is not None:
+            e.set_active_columns(s["nact"])
+        if s["eps"] is not None:
+            e.set_tolerances(*s["eps"])
+        calls = []
+        for budget in s["budgets"]:
+            res = e.solve_dual(budget) if s["dual"] else e.solve(budget, s["rule"])
+            calls.append([r.status for r in res])
+        info = e.info
+        out = _pack(res, e.get_rows(), e.get_basis(), [e.get_log(b) for b in range(B)], calls, info.log_capacity)
+        out["tier"] = np.array(info.tier, dtype=np.int64)
+        out["chunk"] = np.array(info.chunk, dtype=np.int64)
+        return out
+    finally:
+        e.close()
+
+
+def run_oracle(s):
+    """Every LP of the case through oracle.lpo.Oracle, one at a time."""
+    from oracle.lpo import Oracle
+    m, nc = s["m"], ncols_of(s)
+    T, basis = build_tableaus(s)
+    logcap = s["reserve_log"] if s["reserve_log"] is not None else 2 * (m + nc)
+    results, rows, bas, logs, calls = [], [], [], [], [[] for _ in s["budgets"]]
+    for b in range(T.shape[0]):
+        o = Oracle(m, nc)
+        o.load_tableau(T[b], basis[b])
+        if s["nact"] is not None:
+            o.set_active_columns(s["nact"])
+        if s["eps"] is not None:
+            o.set_tolerances(*s["eps"])
+        for c, budget in enumerate(s["budgets"]):
+            r = o.solve_dual(budget) if s["dual"] else o.solve(budget, s["rule"])
+            calls[c].append(r.status)
+        results.append(r)
+        rows.append(o.get_rows())
+        bas.append(o.get_basis())
+        k, rr = o.get_log()
+        logs.append((k[:logcap], rr[:logcap]))      # the batch records the first `capacity` pivots
+        o.close()
+    return _pack(results, np.array(rows), np.array(bas), logs, calls, logcap)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def assert_same(got, want):
+    for key in ("calls", "status", "pivots", "entering", "leaving", "basis", "logcap", "loglen", "logk", "logr"):
+        assert np.array_equal(got[key], want[key]), (key, got[key], want[key])
+    assert np.array_equal(bits(got["objective"]), bits(want["objective"])), "objective bits"
+    diff = np.argwhere(bits(got["rows"]) != bits(want["rows"]))
+    assert diff.size == 0, ("tableau differs first at [LP, row, column]", diff[0].tolist())

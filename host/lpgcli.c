@@ -26,10 +26,11 @@
  *          any HIP call; the parent only relays the host-staged collectives
  *          over socketpairs and never touches a GPU); rank r on device
  *          (D + r) mod #devices; rank 0 prints the JSON line
- *   lpgcli --synthetic M N --batch B [--dual] [--rule ...] [--pivots K] [--seed S]
+ *   lpgcli --synthetic M N --batch B [--dual | --kind ...] [--rule ...] [--pivots K] [--seed S]
  *          B LPs of that shape (seeds S, S + 1, ...) in one lpg_batch, one
  *          workgroup per LP; prints the counts per status, the total pivots
- *          and the LPs/s and pivots/s of the solve call
+ *          and the LPs/s and pivots/s of the solve call; --kind artificial:
+ *          lpg_batch_generate_artificial + lpg_batch_solve_two_phase
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
@@ -64,7 +65,7 @@ static const char *status_name(int s) {
 static int usage(const char *argv0) {
     fprintf(stderr, "Usage:\n\t%s --synthetic M N [--seed S] [--kind dense|degenerate|artificial] [--rule dantzig|bland]"
                     " [--pivots K] [--device D] [--gpus P [--exchange push|host]]\n"
-                    "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate] [--rule dantzig|bland] [--pivots K]"
+                    "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate|artificial] [--rule dantzig|bland] [--pivots K]"
                     " [--seed S]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
@@ -331,15 +332,20 @@ static int run_batch(long long m, long long n, long long count, unsigned long lo
     lpg_batch *b = NULL;
     lpg_result *res = (lpg_result *)malloc((size_t)(count > 0 ? count : 1) * sizeof(lpg_result));
     if (!res) return 1;
+    const int two = kind == LPG_GEN_ARTIFICIAL;
+    int64_t art_first = 0;
     if (lpg_batch_create(&b, device, count, m, n + m + 1, 0) != 0 ||
-        lpg_batch_generate(b, n, seed, dual ? LPG_GEN_DUAL : kind) != 0) {
+        (two ? lpg_batch_generate_artificial(b, n, seed, &art_first)
+             : lpg_batch_generate(b, n, seed, dual ? LPG_GEN_DUAL : kind)) != 0) {
         fprintf(stderr, "ERROR: %s\n", lpg_batch_last_error(b));
         lpg_batch_destroy(b);
         free(res);
         return 1;
     }
     const double t0 = now();
-    const int rc = dual ? lpg_batch_solve_dual(b, pivots, res) : lpg_batch_solve(b, pivots, rule, res);
+    const int rc = two    ? lpg_batch_solve_two_phase(b, art_first, NULL, 0, pivots, rule, res)
+                   : dual ? lpg_batch_solve_dual(b, pivots, res)
+                          : lpg_batch_solve(b, pivots, rule, res);
     const double dt = now() - t0;
     if (rc != 0) {
         fprintf(stderr, "ERROR: %s\n", lpg_batch_last_error(b));
@@ -358,7 +364,7 @@ static int run_batch(long long m, long long n, long long count, unsigned long lo
            "\"method\": \"%s\", \"rule\": \"%s\", \"statuses\": {",
            (long long)info.m, (long long)info.ncols, (long long)info.count,
            info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global", (long long)info.lds_bytes, info.chunk,
-           dual ? "dual" : "primal", rule == LPG_RULE_BLAND && !dual ? "bland" : "dantzig");
+           method_name(kind, dual), rule == LPG_RULE_BLAND && !dual ? "bland" : "dantzig");
     for (int s = 1; s <= 5; s++) printf("%s\"%s\": %lld", s > 1 ? ", " : "", status_name(s), by_status[s]);
     printf("}, \"pivots\": %lld, \"seconds\": %.6f, \"lps_per_s\": %.3f, \"pivots_per_s\": %.3f}\n", total, dt,
            dt > 0 ? (double)count / dt : 0.0, dt > 0 ? (double)total / dt : 0.0);
@@ -561,7 +567,7 @@ int main(int argc, char **argv) {
     if (dual && (bigm || kind == LPG_GEN_ARTIFICIAL)) return usage(argv[0]);
     if (lpfile) return run_lp(lpfile, dump, dual ? LPF_DUAL : bigm ? LPF_BIG_M : LPF_TWO_PHASE, rule, device);
     if (batch >= 0) {
-        if (!(m > 0 && n > 0) || file || gpus > 1 || kind == LPG_GEN_ARTIFICIAL) return usage(argv[0]);
+        if (!(m > 0 && n > 0) || file || gpus > 1) return usage(argv[0]);
         return run_batch(m, n, batch, seed, kind, dual, rule, pivots, device);
     }
     if (gpus > 1) {

@@ -332,7 +332,17 @@ int  lpg_device_sync(lpg_ctx *ctx);
  * cycling LP therefore ends at its budget (LPG_ITER_LIMIT), never in an
  * unbounded kernel.
  *
- * Not supported: two-phase / Big-M batches and mixed shapes (pad with zero
+ * Two-phase: lpg_batch_solve_two_phase runs lpg_solve_two_phase's algorithm
+ * on every LP (lpg_batch.hip k_batch_two_phase): phase I, the feasibility
+ * test, the drive-out of basic artificials and phase II all happen in the
+ * workgroup that owns the LP, an LDS-tier tableau staying in LDS across the
+ * transition, so an LP that finishes phase I early goes on at once. A launch
+ * is bounded here too (a pivot, drive-outs included, or an objective
+ * computation is one unit of `chunk`); the per-LP phase and drive-out cursor
+ * round-trip with the rest of the state and the next launch resumes there.
+ *
+ * Not supported: Big-M batches (they need a second objective row and
+ * lexicographic pricing) and mixed shapes (pad with zero
  * rows or columns, which never pivot); LPG_FLAG_NO_LOG is the only flag.
  * Every argument is validated on the host before any launch. One batch per
  * host thread; not reentrant. */
@@ -365,7 +375,7 @@ int  lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tablea
                     const int64_t *basis);
 /* LP i = lpg_generate(n_struct, seed + i, kind) for every LP of the batch
  * (ncols == n_struct + m + 1); kind: LPG_GEN_DENSE, LPG_GEN_DEGENERATE or
- * LPG_GEN_DUAL. */
+ * LPG_GEN_DUAL (LPG_GEN_ARTIFICIAL: lpg_batch_generate_artificial). */
 int  lpg_batch_generate(lpg_batch *b, int64_t n_struct, uint64_t seed, int kind);
 int  lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt);
 int  lpg_batch_set_active_columns(lpg_batch *b, int64_t nact);   /* price columns 1..nact of every LP */
@@ -381,6 +391,27 @@ int  lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out
  * feasible: else LPG_ERR_STATE, the message names the first offending LP
  * and nothing has pivoted. */
 int  lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out);
+/* lpg_solve_two_phase on every LP, whatever its earlier status: artificial
+ * columns art_first..N (one art_first in 2..N for the whole batch); cost =
+ * count x N real costs of pitch ld_cost >= N, LP by LP, or NULL: -1 x each
+ * LP's objective row as it stands at the call. Phase I may apply max_pivots
+ * pivots, phase II max(0, max_pivots - the LP's pivots so far); drive-out
+ * pivots are counted and logged but not charged. A second call starts phase
+ * I again from the current basis. Per LP: LPG_INFEASIBLE (or the phase-I
+ * LPG_ITER_LIMIT / LPG_NUMERIC) with the phase-I tableau, else the phase-II
+ * result. Afterwards the batch's active columns are 1..art_first-1 (as after
+ * lpg_batch_set_active_columns(b, art_first - 1)). Bad art_first, rule,
+ * ld_cost or max_pivots < 0: LPG_ERR_ARG, the message names the argument and
+ * nothing has pivoted. */
+int  lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost,
+                               int64_t max_pivots, int rule, lpg_result *out);
+/* lpg_set_objective on every LP: cost = count x N of pitch ld_cost >= N; the
+ * objective row of LP i becomes d_j = sum_r c_B(r) T[r][j] - c_j from its
+ * current basis, and the LP's status LPG_RUNNING. */
+int  lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost);
+/* LP i = lpg_generate(n_struct, seed + i, LPG_GEN_ARTIFICIAL);
+ * *art_first (may be NULL) = 1 + n_struct + ceil(m / 2). */
+int  lpg_batch_generate_artificial(lpg_batch *b, int64_t n_struct, uint64_t seed, int64_t *art_first);
 /* n x (m+1) rows of pitch ld >= ncols / n x m basis entries of LPs [first, first + n) */
 int  lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld);
 int  lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis);

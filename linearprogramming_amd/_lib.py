@@ -123,6 +123,10 @@ PROTOTYPES = [
     ("lpg_batch_reserve_log", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     ("lpg_batch_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
     ("lpg_batch_solve_dual", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Result)]),
+    ("lpg_batch_solve_two_phase", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
+    ("lpg_batch_set_objective", ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64]),
+    ("lpg_batch_generate_artificial", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, c_int64_p]),
     ("lpg_batch_get_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64]),
     ("lpg_batch_get_basis", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p]),
     ("lpg_batch_get_log", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p, ctypes.c_int64]),

@@ -53,7 +53,26 @@ struct BatchLP {              // 64 B of state per LP
     int64_t last_k, last_r;
     int64_t budget;           // pivots the current solve call may still apply
     double  objective;        // T[m][0] after the last launch
-    int64_t pad[2];
+    int32_t phase;            // two-phase: where the LP stands (PH_*); round-trips between launches
+    int32_t pad;
+    int64_t cursor;           // two-phase: the next row the drive-out looks at
+};
+static_assert(sizeof(BatchLP) == 64, "BatchLP is 64 bytes");
+
+// k_batch_two_phase's per-LP state machine: a launch may end
+// in front of any of these steps and the next one resumes there
+enum : int32_t {
+    PH_OBJ1 = 0,              // save the costs (cost == NULL), phase-I objective
+    PH_LOOP1,                 // phase-I pivots, then the feasibility test
+    PH_DRIVE,                 // drive basic artificials out, row `cursor` next
+    PH_OBJ2,                  // phase-II objective from the real costs, phase-II budget
+    PH_LOOP2,                 // phase-II pivots
+};
+
+struct TwoPhase {
+    double *cost;             // count x N real costs (written by the kernel when save_cost)
+    int64_t art_first, max_pivots;
+    int32_t save_cost;        // cost == NULL: the costs are -1 x the objective row at the call
 };
 
 struct BatchGeo {
@@ -92,8 +111,10 @@ __global__ __launch_bounds__(kBlock) void k_batch_generate(BatchGeo g, int64_t n
                     x = uniform01(kA, (uint64_t)(i * n + jj));
                     if (kind == 3) x = -x;
                 } else {
-                    if (jj < i) x = uniform01(kA, (uint64_t)(i * n + jj)) / (double)(i + 1);
-                    else if (jj == i) x = 1.0;
+                    if (jj < i) {
+                        x = uniform01(kA, (uint64_t)(i * n + jj)) / (double)(i + 1);
+                        if (kind == 2 && !(i & 1)) x = -x;     // artificial: even rows are feasible `<= 0` rows
+                    } else if (jj == i) x = 1.0;
                 }
             } else if (j == unit_column(g.m, n, i, kind)) {
                 x = 1.0;
@@ -135,6 +156,87 @@ __global__ __launch_bounds__(kBlock) void k_batch_dual_check(BatchGeo g, unsigne
 }
 
 // ------------------------------------------------------------------------
+// the steps of one pivot, shared by k_batch_solve and k_batch_two_phase
+// (whole-block calls from uniform control flow; results uniform)
+// ------------------------------------------------------------------------
+
+// pricing over columns 1..nact of the objective row (lpo.c price): the entering column or -1
+template <int RULE>
+__device__ __forceinline__ int64_t batch_price(const double *obj, int64_t nact, double eps_opt, int tid) {
+    PricePart pb{0.0, -1, 0, 0};
+    for (int64_t j = 1 + tid; j <= nact; j += kBlock) {
+        const double d = obj[j];
+        PricePart c{d, d < -eps_opt ? j : -1, 0, (int32_t)j};
+        pp_take(pb, c, pp_better<RULE>(c, pb));
+    }
+    pb = block_argmin_pp<RULE>(pb);
+    return pb.j;
+}
+
+// ratio test of column k (lpo.c ratio_block, cand_less): row < 0 when there is none
+template <int RULE, int TIER>
+__device__ __forceinline__ Cand batch_ratio(const double *T, int64_t tp, int64_t m, int64_t k, const int32_t *sB,
+                                            const int64_t *gB, double eps_piv, int tid) {
+    Cand cb{0.0, 0.0, 0, -1};
+    for (int64_t i = tid; i < m; i += kBlock) {
+        const double a = T[i * tp + k], bi = T[i * tp];
+        Cand c;
+        c.theta = bi > 0.0 ? bi / a : 0.0;
+        c.piv = a;
+        c.key = RULE == RULE_BLAND ? (TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]) : i;
+        c.row = a > eps_piv ? i : -1;
+        cand_take(cb, c, cand_better(c, cb));
+    }
+    return block_argmin_cand(cb);
+}
+
+// lpo_pivot's arithmetic on (k, r) with pivot element piv; the caller records
+// the basis and the log and puts a barrier behind them
+__device__ __forceinline__ void batch_pivot(double *T, int64_t tp, int64_t rows, int64_t ncols, double *sP, double *sC,
+                                            int64_t k, int64_t r, double piv, int tid, int tx, int ty, int j0, int i0) {
+    // P, C
+    for (int64_t j = tid; j < ncols; j += kBlock) sP[j] = T[r * tp + j] / piv;
+    for (int64_t i = tid; i < rows; i += kBlock) sC[i] = T[i * tp + k];
+    __syncthreads();
+    // rank-1 update (lpo_pivot)
+    // a thread keeps its column's P[j] and walks the rows four at a time:
+    // the four loads are issued before the first store, so their latencies
+    // overlap (the compiler cannot reorder them itself: T, P and C may alias)
+    for (int64_t j = j0; j < ncols; j += tx) {
+        const double pj = sP[j];
+        double *col = T + j;
+        int64_t i = i0;
+        for (; i + 3 * ty < rows; i += 4 * ty) {
+            double c[4], t[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                c[u] = sC[i + u * ty];
+                t[u] = col[(i + u * ty) * tp];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) col[(i + u * ty) * tp] = (i + u * ty == r) ? pj : fma(-c[u], pj, t[u]);
+        }
+        for (; i < rows; i += ty) col[i * tp] = (i == r) ? pj : fma(-sC[i], pj, col[i * tp]);
+    }
+}
+
+// lpo.c set_objective_row: d_j = sum_i c_B(i) T[i][j] - c_j, per column one
+// fma chain over the rows in order (lane = column: conflict-free in LDS,
+// coalesced in device memory; rows are never reduced across lanes). cB[i]
+// holds c_B(i); PHASE1: c_j = -1 from art_first on and 0 before, else cost[j-1].
+template <bool PHASE1>
+__device__ __forceinline__ void batch_objective(double *T, int64_t tp, int64_t m, int64_t ncols, const double *cB,
+                                                const double *cost, int64_t art_first, int tid) {
+    for (int64_t j = tid; j < ncols; j += kBlock) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int64_t i = 0; i < m; i++) acc = fma(cB[i], T[i * tp + j], acc);
+        if (j > 0) acc = acc - (PHASE1 ? (j >= art_first ? -1.0 : 0.0) : cost[j - 1]);
+        T[m * tp + j] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------
 // the pivot loop of one LP
 // ------------------------------------------------------------------------
 template <int MODE, int TIER>
@@ -173,14 +275,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
         double piv;
         if constexpr (MODE != MODE_DUAL) {
             // pricing (lpo.c price): also the final peek when the budget is spent
-            PricePart pb{0.0, -1, 0, 0};
-            for (int64_t j = 1 + tid; j <= g.nact; j += kBlock) {
-                const double d = T[m * tp + j];
-                PricePart c{d, d < -g.eps_opt ? j : -1, 0, (int32_t)j};
-                pp_take(pb, c, pp_better<MODE>(c, pb));
-            }
-            pb = block_argmin_pp<MODE>(pb);
-            k = pb.j;
+            k = batch_price<MODE>(T + m * tp, g.nact, g.eps_opt, tid);
             if (k < 0) {
                 status = OPTIMAL;
                 break;
@@ -190,17 +285,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
                 break;
             }
             // ratio test (lpo.c ratio_block, cand_less)
-            Cand cb{0.0, 0.0, 0, -1};
-            for (int64_t i = tid; i < m; i += kBlock) {
-                const double a = T[i * tp + k], bi = T[i * tp];
-                Cand c;
-                c.theta = bi > 0.0 ? bi / a : 0.0;
-                c.piv = a;
-                c.key = MODE == RULE_BLAND ? (TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]) : i;
-                c.row = a > g.eps_piv ? i : -1;
-                cand_take(cb, c, cand_better(c, cb));
-            }
-            cb = block_argmin_cand(cb);
+            const Cand cb = batch_ratio<MODE, TIER>(T, tp, m, k, sB, gB, g.eps_piv, tid);
             r = cb.row;
             if (r < 0) {
                 status = UNBOUNDED;
@@ -248,30 +333,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
             }
             piv = cb.piv;
         }
-        // P, C
-        for (int64_t j = tid; j < ncols; j += kBlock) sP[j] = T[r * tp + j] / piv;
-        for (int64_t i = tid; i < rows; i += kBlock) sC[i] = T[i * tp + k];
-        __syncthreads();
-        // rank-1 update (lpo_pivot)
-        // a thread keeps its column's P[j] and walks the rows four at a time:
-        // the four loads are issued before the first store, so their latencies
-        // overlap (the compiler cannot reorder them itself: T, P and C may alias)
-        for (int64_t j = j0; j < ncols; j += tx) {
-            const double pj = sP[j];
-            double *col = T + j;
-            int64_t i = i0;
-            for (; i + 3 * ty < rows; i += 4 * ty) {
-                double c[4], t[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    c[u] = sC[i + u * ty];
-                    t[u] = col[(i + u * ty) * tp];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) col[(i + u * ty) * tp] = (i + u * ty == r) ? pj : fma(-c[u], pj, t[u]);
-            }
-            for (; i < rows; i += ty) col[i * tp] = (i == r) ? pj : fma(-sC[i], pj, col[i * tp]);
-        }
+        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, piv, tid, tx, ty, j0, i0);
         if (tid == 0) {
             gB[r] = k;
             if (TIER == TIER_LDS) sB[r] = (int32_t)k;
@@ -304,6 +366,202 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
     }
 }
 
+// ------------------------------------------------------------------------
+// two-phase simplex of one LP (lpo.c lpo_solve_two_phase), both phases and
+// the transition between them in the workgroup that owns the LP
+// ------------------------------------------------------------------------
+
+// a two-phase call begins: every LP starts phase I again, whatever its status
+__global__ void k_batch_begin_two_phase(BatchLP *lp, int64_t count, int64_t budget) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= count) return;
+    lp[q].budget = budget;
+    lp[q].status = RUNNING;
+    lp[q].phase = PH_OBJ1;
+    lp[q].cursor = 0;
+}
+
+// Work of a launch: a pivot (drive-outs included) or an objective computation
+// is one unit, and a launch ends in front of the unit that would exceed
+// g.chunk. `budget` is the oracle's: phase I may apply max_pivots pivots,
+// phase II max(0, max_pivots - pivots of the LP); drive-outs are not charged.
+template <int RULE, int TIER>
+__global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase t) {
+    extern __shared__ double smem[];
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    BatchLP *lp = g.lp + b;
+    if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
+    const int64_t m = g.m, rows = m + 1, ncols = g.ncols, af = t.art_first;
+    double *gT = g.T + b * rows * g.ld;
+    int64_t *gB = g.basis + b * m;
+    double *cost = t.cost + b * (ncols - 1);
+    // LDS as k_batch_solve: [tableau (TIER_LDS)] P[ncols] C[rows] [basis as int32 (TIER_LDS)]
+    const int64_t tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
+    double *T = TIER == TIER_LDS ? smem : gT;
+    double *sP = TIER == TIER_LDS ? smem + rows * tp : smem;
+    double *sC = sP + ncols;
+    int32_t *sB = (int32_t *)(sC + rows);
+    const int tx = 1 << g.txs, ty = kBlock >> g.txs;
+    const int j0 = tid & (tx - 1), i0 = tid >> g.txs;
+
+    int32_t phase = lp->phase, pst = lp->pstatus;
+    int64_t cursor = lp->cursor, pivots = lp->pivots, budget = lp->budget;
+    int64_t last_k = lp->last_k, last_r = lp->last_r;
+    const int64_t chunk = g.chunk;
+    if (TIER == TIER_LDS) {
+        for (int64_t i = i0; i < rows; i += ty)
+            for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * g.ld + j];
+        for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
+    }
+    __syncthreads();
+
+    // (k, r) with pivot element piv: the update, the basis, the log, the counters
+    auto apply = [&](int64_t k, int64_t r, double piv) {
+        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, piv, tid, tx, ty, j0, i0);
+        if (tid == 0) {
+            gB[r] = k;
+            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
+            if (g.logk && pivots < g.logcap) {
+                g.logk[b * g.logcap + pivots] = (int32_t)k;
+                g.logr[b * g.logcap + pivots] = (int32_t)r;
+            }
+        }
+        last_k = k;
+        last_r = r;
+        pivots++;
+        __syncthreads();
+    };
+
+    int32_t status = RUNNING;                     // stays RUNNING where the launch ends in front of a unit
+    int64_t work = 0;
+    for (;;) {
+        if (phase == PH_OBJ1 || phase == PH_OBJ2) {
+            if (work >= chunk) break;
+            if (phase == PH_OBJ1 && t.save_cost) {
+                for (int64_t j = 1 + tid; j < ncols; j += kBlock) cost[j - 1] = -T[m * tp + j];
+            }
+            for (int64_t i = tid; i < m; i += kBlock) {
+                const int64_t bi = TIER == TIER_LDS ? (int64_t)sB[i] : gB[i];
+                // (a batch that was never given a basis holds zeros: no column, no cost)
+                sC[i] = phase == PH_OBJ1 ? (bi >= af ? -1.0 : 0.0) : (bi >= 1 ? cost[bi - 1] : 0.0);
+            }
+            __syncthreads();
+            if (phase == PH_OBJ1) batch_objective<true>(T, tp, m, ncols, sC, cost, af, tid);
+            else batch_objective<false>(T, tp, m, ncols, sC, cost, af, tid);
+            __syncthreads();
+            pst = RUNNING;                        // lpo_set_objective
+            if (phase == PH_OBJ2) budget = t.max_pivots > pivots ? t.max_pivots - pivots : 0;
+            phase++;
+            work++;
+            continue;
+        }
+        if (phase == PH_LOOP1 || phase == PH_LOOP2) {
+            // lpo_solve over columns 1..N (phase I) or 1..art_first-1 (phase II)
+            const int64_t nact = phase == PH_LOOP1 ? ncols - 1 : af - 1;
+            int32_t st = RUNNING;
+            for (;;) {
+                const int64_t k = batch_price<RULE>(T + m * tp, nact, g.eps_opt, tid);   // also the final peek
+                if (k < 0) {
+                    st = OPTIMAL;
+                    break;
+                }
+                if (budget == 0) {
+                    st = ITER_LIMIT;
+                    break;
+                }
+                if (work >= chunk) break;
+                const Cand cb = batch_ratio<RULE, TIER>(T, tp, m, k, sB, gB, g.eps_piv, tid);
+                if (cb.row < 0) {
+                    st = UNBOUNDED;
+                    break;
+                }
+                if (!isfinite(cb.piv) || !isfinite(T[cb.row * tp])) {
+                    st = NUMERIC;
+                    break;
+                }
+                apply(k, cb.row, cb.piv);
+                budget--;
+                work++;
+            }
+            if (st == RUNNING) break;             // the launch's work is done; this loop goes on in the next
+            if (st != ITER_LIMIT) pst = st;       // lpo_ctx.status
+            if (phase == PH_LOOP2 || st == ITER_LIMIT || st == NUMERIC) {
+                status = st;
+                break;
+            }
+            if (st == UNBOUNDED) {                // the phase-I objective is bounded: arithmetic went wrong
+                status = NUMERIC;
+                break;
+            }
+            // feasibility: every thread adds the same column in row order
+            double bsum = 0;
+            for (int64_t i = 0; i < m; i++) bsum += fabs(T[i * tp]);
+            if (T[m * tp] < -1e-9 * (bsum > 1.0 ? bsum : 1.0)) {
+                status = INFEASIBLE;
+                break;
+            }
+            phase = PH_DRIVE;
+            cursor = 0;
+            continue;
+        }
+        // PH_DRIVE: a basic artificial leaves on the first real column with a usable entry in its
+        // row, of either sign (b_i is zero there; no ratio test); a row without one keeps it
+        bool full = false;
+        for (; cursor < m; cursor++) {
+            if ((TIER == TIER_LDS ? (int64_t)sB[cursor] : gB[cursor]) < af) continue;
+            PricePart pb{0.0, -1, 0, 0};
+            for (int64_t j = 1 + tid; j < af; j += kBlock) {
+                const double a = T[cursor * tp + j];
+                PricePart c{a, fabs(a) > g.eps_piv ? j : -1, 0, (int32_t)j};
+                pp_take(pb, c, pp_better<RULE_BLAND>(c, pb));
+            }
+            pb = block_argmin_pp<RULE_BLAND>(pb);  // the smallest such column
+            if (pb.j < 0) continue;
+            if (work >= chunk) {
+                full = true;
+                break;
+            }
+            apply(pb.j, cursor, pb.v);
+            work++;
+        }
+        if (full) break;
+        phase = PH_OBJ2;
+    }
+
+    // store the state
+    if (TIER == TIER_LDS && work > 0) {
+        for (int64_t i = i0; i < rows; i += ty)
+            for (int64_t j = j0; j < ncols; j += tx) gT[i * g.ld + j] = T[i * tp + j];
+    }
+    if (tid == 0) {
+        lp->status = status;
+        lp->pstatus = pst;
+        lp->pivots = pivots;
+        lp->last_k = last_k;
+        lp->last_r = last_r;
+        lp->budget = budget;
+        lp->objective = T[m * tp];
+        lp->phase = phase;
+        lp->cursor = cursor;
+        if (status == RUNNING) atomicAdd(g.running, 1);
+    }
+}
+
+// lpo_set_objective on every LP, costs as k_batch_two_phase's (count x N)
+__global__ __launch_bounds__(kBlock) void k_batch_set_objective(BatchGeo g, const double *costs) {
+    const int64_t b = blockIdx.x, m = g.m;
+    double *T = g.T + b * (m + 1) * g.ld;
+    const int64_t *gB = g.basis + b * m;
+    const double *cost = costs + b * (g.ncols - 1);
+    for (int64_t j = threadIdx.x; j < g.ncols; j += kBlock) {
+        double acc = 0.0;
+        for (int64_t i = 0; i < m; i++) acc = fma(gB[i] >= 1 ? cost[gB[i] - 1] : 0.0, T[i * g.ld + j], acc);
+        T[m * g.ld + j] = j == 0 ? acc : acc - cost[j - 1];
+    }
+    if (threadIdx.x == 0) g.lp[b].status = g.lp[b].pstatus = RUNNING;
+}
+
 }  // namespace lpg
 
 // ---------------------------------------------------------------------------
@@ -328,6 +586,7 @@ struct lpg_batch {
     int32_t *logk = nullptr, *logr = nullptr;
     int32_t *running = nullptr;
     unsigned long long *bad = nullptr;
+    double *cost = nullptr;       // count x N real costs of two-phase calls / set_objective (allocated on first use)
     hipStream_t stream = nullptr;
     char err[512] = {0};
 };
@@ -437,7 +696,46 @@ int launch_solve(lpg_batch *b, int mode) {
     }
 }
 
-int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out) {
+template <int RULE, int TIER>
+int launch_two_phase_t(lpg_batch *b, const TwoPhase &t) {
+    static std::atomic<unsigned long long> attr{0};
+    const int dev = b->device & 63;
+    if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
+        if (hipFuncSetAttribute((const void *)k_batch_two_phase<RULE, TIER>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kBatchMaxLds) != hipSuccess) {
+            (void)hipGetLastError();
+            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(k_batch_two_phase, %d bytes of LDS) failed", kBatchMaxLds);
+        }
+        attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
+    }
+    hipLaunchKernelGGL((k_batch_two_phase<RULE, TIER>), dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream,
+                       bgeo(b), t);
+    return 0;
+}
+
+int launch_two_phase(lpg_batch *b, int rule, const TwoPhase &t) {
+    const bool l = b->tier == TIER_LDS;
+    if (rule == RULE_BLAND) return l ? launch_two_phase_t<RULE_BLAND, TIER_LDS>(b, t) : launch_two_phase_t<RULE_BLAND, TIER_GLOBAL>(b, t);
+    return l ? launch_two_phase_t<RULE_DANTZIG, TIER_LDS>(b, t) : launch_two_phase_t<RULE_DANTZIG, TIER_GLOBAL>(b, t);
+}
+
+// the batch's count x N cost buffer, filled from the host's (pitch ld_cost) when given
+int stage_costs(lpg_batch *b, const double *cost, int64_t ld_cost) {
+    const int64_t N = b->ncols - 1;
+    if (!b->cost && hipMalloc(&b->cost, (size_t)b->count * (size_t)N * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        b->cost = nullptr;
+        return bfail(b, LPG_ERR_OOM, "hipMalloc(costs of %lld LPs) failed", (long long)b->count);
+    }
+    if (cost)
+        BHIPCHK(b, hipMemcpy2DAsync(b->cost, (size_t)N * sizeof(double), cost, (size_t)ld_cost * sizeof(double),
+                                    (size_t)N * sizeof(double), (size_t)b->count, hipMemcpyHostToDevice, b->stream));
+    if (cost) BHIPCHK(b, hipStreamSynchronize(b->stream));        // the caller's array is free again
+    return 0;
+}
+
+// two == nullptr: k_batch_solve in `mode`; else k_batch_two_phase with rule `mode`
+int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const TwoPhase *two = nullptr) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "max_pivots < 0");
     BHIPCHK(b, hipSetDevice(b->device));
@@ -453,16 +751,23 @@ int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out) {
             return bfail(b, LPG_ERR_STATE, "lpg_batch_solve_dual: LP %llu is not dual feasible (a d_j < -eps_opt); "
                                            "nothing has pivoted", bad);
     }
-    hipLaunchKernelGGL(k_batch_begin, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, b->count,
-                       max_pivots, mode == MODE_DUAL ? 1 : 0);
+    if (two)
+        hipLaunchKernelGGL(k_batch_begin_two_phase, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp,
+                           b->count, max_pivots);
+    else
+        hipLaunchKernelGGL(k_batch_begin, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, b->count,
+                           max_pivots, mode == MODE_DUAL ? 1 : 0);
     BHIPCHK(b, hipGetLastError());
     b->pivoted = true;
-    // every launch spends `chunk` of each running LP's budget (or ends the LP)
-    const int64_t max_launches = max_pivots / b->chunk + 2;
+    // every launch spends `chunk` of each running LP's budget (or ends the LP);
+    // two-phase: both phases have a budget of up to max_pivots, and the
+    // drive-out pivots (at most m) and the two objectives are work as well
+    int64_t max_launches = max_pivots / b->chunk + 2;
+    if (two) max_launches = 2 * std::min<int64_t>(max_pivots / b->chunk, (int64_t)1 << 60) + (b->m + 2) / b->chunk + 4;
     for (int64_t it = 0;; it++) {
         int32_t running = 0;
         BHIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
-        if (int rc = launch_solve(b, mode)) return rc;
+        if (int rc = two ? launch_two_phase(b, mode, *two) : launch_solve(b, mode)) return rc;
         BHIPCHK(b, hipGetLastError());
         BHIPCHK(b, hipMemcpyAsync(&running, b->running, sizeof running, hipMemcpyDeviceToHost, b->stream));
         BHIPCHK(b, hipStreamSynchronize(b->stream));
@@ -597,6 +902,7 @@ void lpg_batch_destroy(lpg_batch *b) {
     if (b->logr) (void)hipFree(b->logr);
     if (b->running) (void)hipFree(b->running);
     if (b->bad) (void)hipFree(b->bad);
+    if (b->cost) (void)hipFree(b->cost);
     delete b;
 }
 
@@ -687,6 +993,58 @@ int lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out)
 
 int lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out) {
     return batch_run(b, max_pivots, MODE_DUAL, out);
+}
+
+int lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
+                              int rule, lpg_result *out) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    const int64_t N = b->ncols - 1;
+    if (art_first < 2 || art_first > N)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: art_first %lld outside 2..%lld", (long long)art_first,
+                     (long long)N);
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: rule %d", rule);
+    if (cost && ld_cost < N)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: ld_cost %lld < N = %lld", (long long)ld_cost, (long long)N);
+    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: max_pivots < 0");
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
+    TwoPhase t{};
+    t.cost = b->cost;
+    t.art_first = art_first;
+    t.max_pivots = max_pivots;
+    t.save_cost = cost ? 0 : 1;
+    b->nact = art_first - 1;          // what phase II prices, and what a later lpg_batch_solve goes on with
+    return batch_run(b, max_pivots, rule, out, &t);
+}
+
+int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
+    if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: NULL argument");
+    if (ld_cost < b->ncols - 1)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: ld_cost %lld < N = %lld", (long long)ld_cost,
+                     (long long)(b->ncols - 1));
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
+    hipLaunchKernelGGL(k_batch_set_objective, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b), b->cost);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_t *art_first) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (n < 1 || b->ncols != n + b->m + 1)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_generate_artificial: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
+                     (long long)(n + b->m + 1));
+    BHIPCHK(b, hipSetDevice(b->device));
+    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + 1))), dim3(kBlock), 0, b->stream, bgeo(b), n,
+                       seed, (int)LPG_GEN_ARTIFICIAL);
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    b->pivoted = false;
+    if (art_first) *art_first = 1 + n + (b->m + 1) / 2;
+    return 0;
 }
 
 int lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld) {

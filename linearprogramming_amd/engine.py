@@ -370,6 +370,39 @@ class BatchEngine:
         self._check(self.lib.lpg_batch_solve_dual(self._b, max_pivots, r), "lpg_batch_solve_dual")
         return [_res(x) for x in r]
 
+    def _costs(self, cost, what):
+        """cost: [N] (the same for every LP) or [count, >= N] -> a C-contiguous array, its pointer and pitch."""
+        c = np.asarray(cost, dtype=np.float64)
+        if c.ndim == 1:
+            c = np.tile(c, (self.count, 1))
+        c = np.ascontiguousarray(c)
+        if c.ndim != 2 or c.shape[0] != self.count:
+            raise LPGError(f"{what}: costs of shape {c.shape}, want [{self.count}, >= {self.ncols - 1}]")
+        return c, c.ctypes.data_as(L.c_double_p), c.shape[1]
+
+    def solve_two_phase(self, art_first: int, cost=None, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> list:
+        """Engine.solve_two_phase on every LP in one launch; cost: None, [N] or [count, >= N]
+        (the row pitch is the array's width). Afterwards columns 1..art_first-1 are active."""
+        keep, cp, ld = (None, None, 0) if cost is None else self._costs(cost, "solve_two_phase")
+        r = (L.Result * self.count)()
+        self._check(self.lib.lpg_batch_solve_two_phase(self._b, art_first, cp, ld, max_pivots, rule, r),
+                    "lpg_batch_solve_two_phase")
+        del keep
+        return [_res(x) for x in r]
+
+    def set_objective(self, cost):
+        """Engine.set_objective on every LP; cost: [N] or [count, >= N]."""
+        keep, cp, ld = self._costs(cost, "set_objective")
+        self._check(self.lib.lpg_batch_set_objective(self._b, cp, ld), "lpg_batch_set_objective")
+        del keep
+
+    def generate_artificial(self, n: int, seed: int = 20220518) -> int:
+        """LP b = Engine.generate(n, seed + b, GEN_ARTIFICIAL); returns art_first."""
+        af = ctypes.c_int64(0)
+        self._check(self.lib.lpg_batch_generate_artificial(self._b, n, seed, ctypes.byref(af)),
+                    "lpg_batch_generate_artificial")
+        return int(af.value)
+
     # -- readout ---------------------------------------------------------
     def get_rows(self, first: int = 0, n: int = None) -> np.ndarray:
         n = self.count - first if n is None else n

@@ -650,17 +650,14 @@ class LPSolution:
     method: str = "primal"
 
 
-def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) -> LPSolution:
-    """The bridge's device solve (integration/lpg_bridge.c LPGSolveSMatrix) on liblpg:
-    rows without a true unit basic column get artificials (two-phase by default,
-    ``method="big_m"`` for Big-M; ``method="dual"``: the dual simplex from the
-    slack basis of a dual-form SimplexMatrix, which must be complete and dual
-    feasible); the readout un-substitutes x <= 0 and free variables as the
-    reference's variable table records them."""
-    from . import _lib as L
-    from .engine import Engine
-    if rule is None:
-        rule = L.RULE_DANTZIG
+def engine_arrays(sm: SMatrix):
+    """What solve() and solve_batch() hand to the engine for ``sm``:
+    (rows [m, nc] float64, basis [m] int64, cost [nc] float64, nc0, nlack).
+    Columns 0..nc0-1 are the SimplexMatrix's [b | a_1..a_N]; a row without a
+    true unit basic column gets an artificial unit column (nc0 .., in row
+    order: art_first = nc0, nlack of them, nc = nc0 + nlack); cost holds the
+    max-form costs and zeros for the artificials (the engine's N = nc - 1
+    entries and one unused trailing zero)."""
     m, nc0 = len(sm.rows), len(sm.names) + 1
     basis = list(sm.basis)
     for i in range(m):                              # keep a basic column only if it is a true unit column
@@ -668,11 +665,6 @@ def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) ->
         if j and any(sm.rows[q][j] != (1 if q == i else 0) for q in range(m)):
             basis[i] = 0
     nlack = sum(1 for b in basis if b == 0)
-    if method == "dual":
-        if nlack:
-            raise FrontendError("dual simplex: rows without a slack basis (equality rows); use build_smatrix(text, dual=True)")
-        if any(_dec(c) > 0 for c in sm.costs):
-            raise FrontendError("dual simplex: the slack basis is not dual feasible (a positive max-form cost)")
     nc = nc0 + nlack
     rows = np.zeros((m, nc), dtype=np.float64)
     for i, r in enumerate(sm.rows):
@@ -685,6 +677,94 @@ def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) ->
             a += 1
     cost = np.zeros(nc, dtype=np.float64)
     cost[:nc0 - 1] = [_dec(c) for c in sm.costs]
+    return rows, np.asarray(basis, dtype=np.int64), cost, nc0, nlack
+
+
+def _readout(sm: SMatrix, sol: LPSolution, objective: float, xb, bas, nc: int) -> LPSolution:
+    """The optimum's z, columns and un-substituted variables from x_B and the basis."""
+    x = np.zeros(nc, dtype=np.float64)
+    for i in range(len(bas)):
+        x[bas[i] - 1] = xb[i]
+    sol.z = (objective + _dec(sm.constant)) / _dec(sm.zcoef)
+    sol.columns = {v: float(x[j]) for j, v in enumerate(sm.display_names)}
+    val = {v: float(x[j]) for j, v in enumerate(sm.names)}
+    for it in sm.vars.ordered():
+        if it.relation == 0 and it.former:
+            sol.variables[it.name] = val.get(it.former, 0.0) - val.get(it.latter, 0.0)
+        elif it.relation < 0 and it.number == 0:
+            sol.variables[it.name] = -val.get(it.name, 0.0)
+        else:
+            sol.variables[it.name] = val.get(it.name, 0.0)
+    return sol
+
+
+def batch_groups(sms) -> dict:
+    """solve_batch's grouping: {(m, nc0, nlack): [input indices, ascending]}, keys in order of first appearance."""
+    return _groups([engine_arrays(sm) for sm in sms])
+
+
+def _groups(arrays) -> dict:
+    groups = {}
+    for idx, (rows, _, _, nc0, nlack) in enumerate(arrays):
+        groups.setdefault((rows.shape[0], nc0, nlack), []).append(idx)
+    return groups
+
+
+def solve_batch(sms, rule=None, device: int = 0) -> list:
+    """solve(sm) for every SMatrix of ``sms`` (two-phase where rows lack a basic
+    column, the plain primal simplex where none does), the models of one shape
+    (m, nc0, nlack) together in one BatchEngine: one launch per group instead
+    of one engine per model. The result list is in input order and each entry
+    equals solve(sm) field by field, floats bit for bit."""
+    from . import _lib as L
+    from .engine import BatchEngine
+    if rule is None:
+        rule = L.RULE_DANTZIG
+    sms = list(sms)
+    arrays = [engine_arrays(sm) for sm in sms]
+    out = [None] * len(sms)
+    for (m, nc0, nlack), members in _groups(arrays).items():
+        nc = nc0 + nlack
+        T = np.zeros((len(members), m + 1, nc), dtype=np.float64)
+        for q, idx in enumerate(members):
+            T[q, :m] = arrays[idx][0]
+        basis = np.array([arrays[idx][1] for idx in members], dtype=np.int64)
+        cost = np.array([arrays[idx][2] for idx in members], dtype=np.float64)
+        with BatchEngine(len(members), m, nc, device=device) as e:
+            e.load(T, basis)
+            if nlack == 0:
+                e.set_objective(cost)
+                res, used = e.solve(rule=rule), "primal"
+            else:
+                res, used = e.solve_two_phase(nc0, cost, rule=rule), "two_phase"
+            rows, bas = e.get_rows(), e.get_basis()
+        for q, idx in enumerate(members):
+            r = res[q]
+            sol = LPSolution(r.status_name, int(r.pivots), method=used)
+            if r.status == L.OPTIMAL:
+                _readout(sms[idx], sol, r.objective, rows[q, :m, 0], bas[q], nc)
+            out[idx] = sol
+    return out
+
+
+def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) -> LPSolution:
+    """The bridge's device solve (integration/lpg_bridge.c LPGSolveSMatrix) on liblpg:
+    rows without a true unit basic column get artificials (two-phase by default,
+    ``method="big_m"`` for Big-M; ``method="dual"``: the dual simplex from the
+    slack basis of a dual-form SimplexMatrix, which must be complete and dual
+    feasible); the readout un-substitutes x <= 0 and free variables as the
+    reference's variable table records them."""
+    from . import _lib as L
+    from .engine import Engine
+    if rule is None:
+        rule = L.RULE_DANTZIG
+    rows, basis, cost, nc0, nlack = engine_arrays(sm)
+    m, nc = rows.shape
+    if method == "dual":
+        if nlack:
+            raise FrontendError("dual simplex: rows without a slack basis (equality rows); use build_smatrix(text, dual=True)")
+        if any(_dec(c) > 0 for c in sm.costs):
+            raise FrontendError("dual simplex: the slack basis is not dual feasible (a positive max-form cost)")
     bigm = method == "big_m" and nlack > 0
     with Engine(m, nc, device=device, flags=L.FLAG_BIG_M if bigm else 0) as e:
         e.load_rows(0, rows)
@@ -708,20 +788,7 @@ def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) ->
             return sol
         xb = e.get_column0()
         bas = e.get_basis()
-    x = np.zeros(nc, dtype=np.float64)
-    for i in range(m):
-        x[bas[i] - 1] = xb[i]
-    sol.z = (r.objective + _dec(sm.constant)) / _dec(sm.zcoef)
-    sol.columns = {v: float(x[j]) for j, v in enumerate(sm.display_names)}
-    val = {v: float(x[j]) for j, v in enumerate(sm.names)}
-    for it in sm.vars.ordered():
-        if it.relation == 0 and it.former:
-            sol.variables[it.name] = val.get(it.former, 0.0) - val.get(it.latter, 0.0)
-        elif it.relation < 0 and it.number == 0:
-            sol.variables[it.name] = -val.get(it.name, 0.0)
-        else:
-            sol.variables[it.name] = val.get(it.name, 0.0)
-    return sol
+    return _readout(sm, sol, r.objective, xb, bas, nc)
 
 
 def solve_text(text: str, method: str = "two_phase", rule=None, device: int = 0) -> LPSolution:

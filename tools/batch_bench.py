@@ -3,6 +3,11 @@
 
     python tools/batch_bench.py --m 64 --n 128 --batch 1024 [--repeats 5] [--kind dense] [--out FILE]
 
+--kind artificial: the generator's artificial LPs (equality rows with
+artificial unit columns) by the two-phase method, (a) generate_artificial +
+BatchEngine.solve_two_phase, (b) generate(kind=GEN_ARTIFICIAL) +
+Engine.solve_two_phase per LP.
+
 (a) one BatchEngine.solve over B LPs (seeds S, S + 1, ...): generate (not
     timed), then the wall time of solve(), which returns after a device
     synchronise and the read-back of every LP's result;
@@ -34,7 +39,7 @@ if ROOT not in sys.path:
 
 CLK_HZ = 2.4e9
 DS_READ_B64_BPC, DS_WRITE_B64_BPC = 256.0, 85.0      # bytes per clock and CU
-KINDS = {"dense": 0, "degenerate": 1}
+KINDS = {"dense": 0, "degenerate": 1, "artificial": 2}
 
 
 def main() -> int:
@@ -55,15 +60,21 @@ def main() -> int:
     m, n, B, nc = a.m, a.n, a.batch, a.n + a.m + 1
     kind, rule = KINDS[a.kind], 1 if a.rule == "bland" else 0
     budget = 50 * (m + n)
+    two = a.kind == "artificial"
     cus = 256
 
     be = lpg.BatchEngine(B, m, nc, device=a.device, flags=lpg._lib.FLAG_NO_LOG)
     info = be.info
 
     def run_batch():
-        be.generate(n, a.seed, kind)
-        t0 = time.perf_counter()
-        res = be.solve(budget, rule)            # ends in a device synchronise + result read-back
+        if two:
+            af = be.generate_artificial(n, a.seed)
+            t0 = time.perf_counter()
+            res = be.solve_two_phase(af, None, budget, rule)
+        else:
+            be.generate(n, a.seed, kind)
+            t0 = time.perf_counter()
+            res = be.solve(budget, rule)        # ends in a device synchronise + result read-back
         return time.perf_counter() - t0, [(r.status, r.pivots) for r in res]
 
     def run_loop():
@@ -72,7 +83,7 @@ def main() -> int:
         for b in range(B):
             e = lpg.Engine(m, nc, device=a.device, flags=lpg._lib.FLAG_NO_LOG)
             e.generate(n, a.seed + b, kind)
-            r = e.solve(budget, rule)           # synchronises
+            r = e.solve_two_phase(1 + n + (m + 1) // 2, None, budget, rule) if two else e.solve(budget, rule)   # synchronises
             out.append((r.status, r.pivots))
             e.close()
         return time.perf_counter() - t0, out

@@ -30,7 +30,8 @@
  *          B LPs of that shape (seeds S, S + 1, ...) in one lpg_batch, one
  *          workgroup per LP; prints the counts per status, the total pivots
  *          and the LPs/s and pivots/s of the solve call; --kind artificial:
- *          lpg_batch_generate_artificial + lpg_batch_solve_two_phase
+ *          lpg_batch_generate_artificial + lpg_batch_solve_two_phase (with
+ *          --big-m: lpg_batch_create_big_m + lpg_batch_solve_big_m)
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
@@ -65,7 +66,7 @@ static const char *status_name(int s) {
 static int usage(const char *argv0) {
     fprintf(stderr, "Usage:\n\t%s --synthetic M N [--seed S] [--kind dense|degenerate|artificial] [--rule dantzig|bland]"
                     " [--pivots K] [--device D] [--gpus P [--exchange push|host]]\n"
-                    "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate|artificial] [--rule dantzig|bland] [--pivots K]"
+                    "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate|artificial [--big-m]] [--rule dantzig|bland] [--pivots K]"
                     " [--seed S]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
@@ -327,14 +328,16 @@ static int run_dist(const dist_args *a) {
 }
 
 /* --batch B: B synthetic LPs of one shape through lpg_batch */
-static int run_batch(long long m, long long n, long long count, unsigned long long seed, int kind, int dual, int rule,
-                     long long pivots, int device) {
+static int run_batch(long long m, long long n, long long count, unsigned long long seed, int kind, int dual, int bigm,
+                     int rule, long long pivots, int device) {
     lpg_batch *b = NULL;
     lpg_result *res = (lpg_result *)malloc((size_t)(count > 0 ? count : 1) * sizeof(lpg_result));
     if (!res) return 1;
     const int two = kind == LPG_GEN_ARTIFICIAL;
+    bigm = bigm && two;                        /* --big-m: the artificial LPs by Big-M in an (m+2)-row batch */
     int64_t art_first = 0;
-    if (lpg_batch_create(&b, device, count, m, n + m + 1, 0) != 0 ||
+    if ((bigm ? lpg_batch_create_big_m(&b, device, count, m, n + m + 1, 0)
+              : lpg_batch_create(&b, device, count, m, n + m + 1, 0)) != 0 ||
         (two ? lpg_batch_generate_artificial(b, n, seed, &art_first)
              : lpg_batch_generate(b, n, seed, dual ? LPG_GEN_DUAL : kind)) != 0) {
         fprintf(stderr, "ERROR: %s\n", lpg_batch_last_error(b));
@@ -343,7 +346,8 @@ static int run_batch(long long m, long long n, long long count, unsigned long lo
         return 1;
     }
     const double t0 = now();
-    const int rc = two    ? lpg_batch_solve_two_phase(b, art_first, NULL, 0, pivots, rule, res)
+    const int rc = bigm   ? lpg_batch_solve_big_m(b, art_first, NULL, 0, pivots, rule, res)
+                   : two  ? lpg_batch_solve_two_phase(b, art_first, NULL, 0, pivots, rule, res)
                    : dual ? lpg_batch_solve_dual(b, pivots, res)
                           : lpg_batch_solve(b, pivots, rule, res);
     const double dt = now() - t0;
@@ -364,7 +368,7 @@ static int run_batch(long long m, long long n, long long count, unsigned long lo
            "\"method\": \"%s\", \"rule\": \"%s\", \"statuses\": {",
            (long long)info.m, (long long)info.ncols, (long long)info.count,
            info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global", (long long)info.lds_bytes, info.chunk,
-           method_name(kind, dual), rule == LPG_RULE_BLAND && !dual ? "bland" : "dantzig");
+           bigm ? "big-m" : method_name(kind, dual), rule == LPG_RULE_BLAND && !dual ? "bland" : "dantzig");
     for (int s = 1; s <= 5; s++) printf("%s\"%s\": %lld", s > 1 ? ", " : "", status_name(s), by_status[s]);
     printf("}, \"pivots\": %lld, \"seconds\": %.6f, \"lps_per_s\": %.3f, \"pivots_per_s\": %.3f}\n", total, dt,
            dt > 0 ? (double)count / dt : 0.0, dt > 0 ? (double)total / dt : 0.0);
@@ -568,7 +572,7 @@ int main(int argc, char **argv) {
     if (lpfile) return run_lp(lpfile, dump, dual ? LPF_DUAL : bigm ? LPF_BIG_M : LPF_TWO_PHASE, rule, device);
     if (batch >= 0) {
         if (!(m > 0 && n > 0) || file || gpus > 1) return usage(argv[0]);
-        return run_batch(m, n, batch, seed, kind, dual, rule, pivots, device);
+        return run_batch(m, n, batch, seed, kind, dual, bigm, rule, pivots, device);
     }
     if (gpus > 1) {
         if (!(m > 0 && n > 0) || gpus > m || gpus > 64) return usage(argv[0]);

@@ -341,14 +341,23 @@ int  lpg_device_sync(lpg_ctx *ctx);
  * computation is one unit of `chunk`); the per-LP phase and drive-out cursor
  * round-trip with the rest of the state and the next launch resumes there.
  *
- * Not supported: Big-M batches (they need a second objective row and
- * lexicographic pricing) and mixed shapes (pad with zero
- * rows or columns, which never pivot); LPG_FLAG_NO_LOG is the only flag.
+ * Big-M: a batch from lpg_batch_create_big_m holds (m+2) x ncols tableaus,
+ * the M part of the objective in row m and the real part in row m + 1 (the
+ * layout of an LPG_FLAG_BIG_M context), and lpg_batch_solve_big_m runs
+ * lpg_solve_big_m's algorithm on every LP (lpg_batch.hip k_batch_big_m: both
+ * objective rows in the rank-1 update, lexicographic pricing). The extra row
+ * counts in the LDS footprint, so the tier boundary lies one row earlier than
+ * for a plain batch. The two kinds of batch are kept apart: the other solve
+ * calls refuse a Big-M batch and lpg_batch_solve_big_m a plain one
+ * (LPG_ERR_STATE, nothing has pivoted).
+ *
+ * Not supported: mixed shapes (pad with zero rows or columns, which never
+ * pivot); LPG_FLAG_NO_LOG is the only flag.
  * Every argument is validated on the host before any launch. One batch per
  * host thread; not reentrant. */
 #define LPG_BATCH_TIER_LDS    0
 #define LPG_BATCH_TIER_GLOBAL 1
-#define LPG_BATCH_MAX_DIM     8192   /* m + 1 and ncols of a batch */
+#define LPG_BATCH_MAX_DIM     8192   /* m + 1 (Big-M: m + 2) and ncols of a batch */
 
 typedef struct lpg_batch lpg_batch;
 
@@ -358,17 +367,26 @@ typedef struct {
     int32_t chunk;                /* pivots per LP and launch */
     int64_t lds_bytes;            /* dynamic LDS of one workgroup */
     int64_t log_capacity;         /* pivots recorded per LP (0 with LPG_FLAG_NO_LOG) */
+    int32_t nobj;                 /* objective rows per tableau: 1, or 2 for a Big-M batch */
+    int32_t pad;
 } lpg_batch_info_t;
 
 /* count >= 1 LPs of m constraint rows and ncols = N+1 columns; flags: 0 or
  * LPG_FLAG_NO_LOG (anything else: LPG_ERR_ARG). All tableaus start as zeros
  * with status LPG_RUNNING; load or generate them next. */
 int  lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags);
+/* The same for a Big-M batch: every tableau is (m+2) x ncols, row m the M
+ * part and row m + 1 the real part of the objective; m + 2 <= LPG_BATCH_MAX_DIM.
+ * Arguments, flags and refusals as lpg_batch_create. lpg_batch_load and
+ * lpg_batch_get_rows then move m + 2 rows per LP, and
+ * lpg_batch_generate_artificial puts the objective into row m + 1 (the M row
+ * is zero). */
+int  lpg_batch_create_big_m(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags);
 void lpg_batch_destroy(lpg_batch *b);                        /* NULL is a no-op */
 const char *lpg_batch_last_error(const lpg_batch *b);        /* NULL: this thread's last create error */
 int  lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *out);
-/* LPs [first, first + n): tableaus = n x (m+1) rows [b | a_1..a_N] of pitch
- * ld >= ncols, objective row last; basis = n x m 1-based basic columns
+/* LPs [first, first + n): tableaus = n x (m+1) rows (Big-M batch: m+2)
+ * [b | a_1..a_N] of pitch ld >= ncols, objective row(s) last; basis = n x m 1-based basic columns
  * (validated: 1..N), or NULL to keep the current ones. The LPs loaded start
  * again: status LPG_RUNNING, no pivots, empty log. */
 int  lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, int64_t ld,
@@ -405,6 +423,19 @@ int  lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out);
  * nothing has pivoted. */
 int  lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost,
                                int64_t max_pivots, int rule, lpg_result *out);
+/* lpg_solve_big_m on every LP of a Big-M batch, whatever its earlier status:
+ * artificial columns art_first..N; cost as lpg_batch_solve_two_phase's, or
+ * NULL: -1 x each LP's row m + 1 as it stands at the call; the entries from
+ * art_first on are taken as 0 in the real row and -1 in the M row. Both
+ * objective rows are recomputed from the current basis, then up to max_pivots
+ * MORE pivots per LP are applied, all columns 1..N priced lexicographically
+ * (M part first). An LP that ends LPG_OPTIMAL or LPG_UNBOUNDED with the M
+ * part of its objective still negative (T[m][0] < -1e-9 max(1, sum |b_i|)) is
+ * LPG_INFEASIBLE. out[].objective is T[m+1][0]. A budget-limited solve goes
+ * on with another call. Argument errors as lpg_batch_solve_two_phase's; a
+ * batch from lpg_batch_create: LPG_ERR_STATE. */
+int  lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost,
+                           int64_t max_pivots, int rule, lpg_result *out);
 /* lpg_set_objective on every LP: cost = count x N of pitch ld_cost >= N; the
  * objective row of LP i becomes d_j = sum_r c_B(r) T[r][j] - c_j from its
  * current basis, and the LP's status LPG_RUNNING. */
@@ -412,7 +443,7 @@ int  lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost);
 /* LP i = lpg_generate(n_struct, seed + i, LPG_GEN_ARTIFICIAL);
  * *art_first (may be NULL) = 1 + n_struct + ceil(m / 2). */
 int  lpg_batch_generate_artificial(lpg_batch *b, int64_t n_struct, uint64_t seed, int64_t *art_first);
-/* n x (m+1) rows of pitch ld >= ncols / n x m basis entries of LPs [first, first + n) */
+/* n x (m+1) rows (Big-M batch: m+2) of pitch ld >= ncols / n x m basis entries of LPs [first, first + n) */
 int  lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld);
 int  lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis);
 /* LP lp's log: copies min(recorded, max) pivots, returns the number recorded

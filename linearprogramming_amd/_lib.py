@@ -57,7 +57,7 @@ class BatchInfo(ctypes.Structure):
     """lpg_batch_info_t."""
     _fields_ = [("count", ctypes.c_int64), ("m", ctypes.c_int64), ("ncols", ctypes.c_int64), ("ld", ctypes.c_int64),
                 ("tier", ctypes.c_int32), ("chunk", ctypes.c_int32), ("lds_bytes", ctypes.c_int64),
-                ("log_capacity", ctypes.c_int64)]
+                ("log_capacity", ctypes.c_int64), ("nobj", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -112,6 +112,8 @@ PROTOTYPES = [
     ("lpg_build_stamp", ctypes.c_char_p, []),
     ("lpg_batch_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                         ctypes.c_int64, ctypes.c_uint32]),
+    ("lpg_batch_create_big_m", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_uint32]),
     ("lpg_batch_destroy", None, [ctypes.c_void_p]),
     ("lpg_batch_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
     ("lpg_batch_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BatchInfo)]),
@@ -125,6 +127,8 @@ PROTOTYPES = [
     ("lpg_batch_solve_dual", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Result)]),
     ("lpg_batch_solve_two_phase", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int64,
                                                  ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
+    ("lpg_batch_solve_big_m", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
     ("lpg_batch_set_objective", ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64]),
     ("lpg_batch_generate_artificial", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, c_int64_p]),
     ("lpg_batch_get_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64]),

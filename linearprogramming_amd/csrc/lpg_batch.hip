@@ -23,6 +23,10 @@
 // state round-trips through device memory; the host relaunches while the
 // device counter of still-running LPs is non-zero. A workgroup whose LP is
 // finished exits at once.
+//
+// Big-M batches (lpg_batch_create_big_m) carry two objective rows per LP, the
+// M part in row m and the real part in row m + 1, and are solved by
+// k_batch_big_m with lexicographic pricing (lpo.c lpo_solve_big_m).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -53,7 +57,7 @@ struct BatchLP {              // 64 B of state per LP
     int64_t last_k, last_r;
     int64_t budget;           // pivots the current solve call may still apply
     double  objective;        // T[m][0] after the last launch
-    int32_t phase;            // two-phase: where the LP stands (PH_*); round-trips between launches
+    int32_t phase;            // two-phase, Big-M: where the LP stands (PH_*); round-trips between launches
     int32_t pad;
     int64_t cursor;           // two-phase: the next row the drive-out looks at
 };
@@ -68,6 +72,8 @@ enum : int32_t {
     PH_OBJ2,                  // phase-II objective from the real costs, phase-II budget
     PH_LOOP2,                 // phase-II pivots
 };
+// k_batch_big_m reuses the first two: PH_OBJ1 = both objective rows are still
+// to be set (costs saved first when cost == NULL), PH_LOOP1 = in the pivot loop
 
 struct TwoPhase {
     double *cost;             // count x N real costs (written by the kernel when save_cost)
@@ -76,7 +82,7 @@ struct TwoPhase {
 };
 
 struct BatchGeo {
-    double  *T;               // count x (m + 1) x ld
+    double  *T;               // count x (m + nobj) x ld
     int64_t *basis;           // count x m
     BatchLP *lp;              // count
     int32_t *logk, *logr;     // count x logcap, or null
@@ -86,13 +92,14 @@ struct BatchGeo {
     int32_t  chunk;
     int32_t  pitch;           // TIER_LDS: row pitch in LDS (doubles, odd)
     int32_t  txs;             // update tile: 1 << txs lanes along a row, 256 >> txs rows at a time
+    int32_t  nobj;            // objective rows: 1, or 2 for a Big-M batch (M part in row m, real part in row m + 1)
 };
 
 // ------------------------------------------------------------------------
 // generator: LP b = lpo_generate(n, seed + b, kind), one block per row
 // ------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_batch_generate(BatchGeo g, int64_t n, uint64_t seed, int kind) {
-    const int64_t rows = g.m + 1;
+    const int64_t rows = g.m + g.nobj;
     const int64_t b = (int64_t)blockIdx.x / rows, i = (int64_t)blockIdx.x % rows;
     const uint64_t s = seed + (uint64_t)b;
     const uint64_t kA = splitmix64(s ^ (1 * 0xD1B54A32D192ED03ull)), kB = splitmix64(s ^ (2 * 0xD1B54A32D192ED03ull)),
@@ -119,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_generate(BatchGeo g, int64_t n
             } else if (j == unit_column(g.m, n, i, kind)) {
                 x = 1.0;
             }
-        } else if (j >= 1 && j <= n) {                 // objective row
+        } else if (i == rows - 1 && j >= 1 && j <= n) {   // (real) objective row; a Big-M M row stays zero
             x = 1.0 + uniform01(kC, (uint64_t)(j - 1));
             if (kind != 3) x = -x;                     // kind 3: max -c.x, d_j = +c_j (dual feasible)
         }
@@ -167,6 +174,24 @@ __device__ __forceinline__ int64_t batch_price(const double *obj, int64_t nact, 
     for (int64_t j = 1 + tid; j <= nact; j += kBlock) {
         const double d = obj[j];
         PricePart c{d, d < -eps_opt ? j : -1, 0, (int32_t)j};
+        pp_take(pb, c, pp_better<RULE>(c, pb));
+    }
+    pb = block_argmin_pp<RULE>(pb);
+    return pb.j;
+}
+
+// Big-M pricing over columns 1..nact of the two objective rows (lpo.c
+// price_class): class 0 where the M part dM < -eps (value dM), class 1 where
+// dM <= eps and the real part dR < -eps (value dR); pp_better and
+// block_argmin_pp order by class first. A NaN dM makes a column ineligible.
+template <int RULE>
+__device__ __forceinline__ int64_t batch_price_big_m(const double *objM, const double *objR, int64_t nact, double eps_opt,
+                                                     int tid) {
+    PricePart pb{0.0, -1, 0, 0};
+    for (int64_t j = 1 + tid; j <= nact; j += kBlock) {
+        const double dM = objM[j], dR = objR[j];
+        const bool c0 = dM < -eps_opt, c1 = (dM <= eps_opt) & (dR < -eps_opt);
+        PricePart c{c0 ? dM : dR, (c0 | c1) ? j : -1, c0 ? 0 : 1, (int32_t)j};
         pp_take(pb, c, pp_better<RULE>(c, pb));
     }
     pb = block_argmin_pp<RULE>(pb);
@@ -548,6 +573,152 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
     }
 }
 
+// ------------------------------------------------------------------------
+// Big-M simplex of one LP (lpo.c lpo_solve_big_m): tableaus of m + 2 rows,
+// the M part of the objective in row m, the real part in row m + 1
+// ------------------------------------------------------------------------
+
+// batch_objective for one of the two rows: MPART: row m from the costs -1 on
+// the artificial columns (art_first on) and 0 before; else row m + 1 from the
+// real costs, those of the artificial columns forced to 0. cB[i] holds c_B(i).
+template <bool MPART>
+__device__ __forceinline__ void batch_objective_big_m(double *T, int64_t tp, int64_t m, int64_t ncols, const double *cB,
+                                                      const double *cost, int64_t art_first, int tid) {
+    double *obj = T + (MPART ? m : m + 1) * tp;
+    for (int64_t j = tid; j < ncols; j += kBlock) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int64_t i = 0; i < m; i++) acc = fma(cB[i], T[i * tp + j], acc);
+        if (j > 0) acc = acc - (j >= art_first ? (MPART ? -1.0 : 0.0) : (MPART ? 0.0 : cost[j - 1]));
+        obj[j] = acc;
+    }
+}
+
+// Work of a launch as k_batch_two_phase's: a pivot or the computation of the
+// two objective rows is one unit. `t.cost` holds the real costs (written here
+// from row m + 1 when save_cost); lp->phase is PH_OBJ1 until the objective
+// rows are set and PH_LOOP1 from then on, so a launch that ends in front of
+// any unit is resumed bitwise by the next.
+template <int RULE, int TIER>
+__global__ __launch_bounds__(kBlock) void k_batch_big_m(BatchGeo g, TwoPhase t) {
+    extern __shared__ double smem[];
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    BatchLP *lp = g.lp + b;
+    if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
+    const int64_t m = g.m, rows = m + 2, ncols = g.ncols, af = t.art_first;
+    double *gT = g.T + b * rows * g.ld;
+    int64_t *gB = g.basis + b * m;
+    double *cost = t.cost + b * (ncols - 1);
+    // LDS: [tableau of m + 2 rows (TIER_LDS)] P[ncols] C[m + 2] [basis as int32 (TIER_LDS)]
+    const int64_t tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
+    double *T = TIER == TIER_LDS ? smem : gT;
+    double *sP = TIER == TIER_LDS ? smem + rows * tp : smem;
+    double *sC = sP + ncols;
+    int32_t *sB = (int32_t *)(sC + rows);
+    const int tx = 1 << g.txs, ty = kBlock >> g.txs;
+    const int j0 = tid & (tx - 1), i0 = tid >> g.txs;
+
+    int32_t phase = lp->phase, pst = lp->pstatus;
+    int64_t pivots = lp->pivots, budget = lp->budget;
+    int64_t last_k = lp->last_k, last_r = lp->last_r;
+    const int64_t chunk = g.chunk;
+    if (TIER == TIER_LDS) {
+        for (int64_t i = i0; i < rows; i += ty)
+            for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * g.ld + j];
+        for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
+    }
+    __syncthreads();
+
+    int32_t status = RUNNING;                     // stays RUNNING where the launch ends in front of a unit
+    int64_t work = 0;
+    if (phase == PH_OBJ1) {
+        // lpo_set_objective_m, lpo_set_objective: each row from the current basis (rows 0..m-1 only)
+        if (t.save_cost) {
+            for (int64_t j = 1 + tid; j < ncols; j += kBlock) cost[j - 1] = -T[(m + 1) * tp + j];
+            __syncthreads();                      // the costs of the basic columns are read by other threads
+        }
+        for (int64_t i = tid; i < m; i += kBlock)
+            sC[i] = (TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]) >= af ? -1.0 : 0.0;
+        __syncthreads();
+        batch_objective_big_m<true>(T, tp, m, ncols, sC, cost, af, tid);
+        __syncthreads();
+        for (int64_t i = tid; i < m; i += kBlock) {
+            const int64_t bi = TIER == TIER_LDS ? (int64_t)sB[i] : gB[i];
+            // (a batch that was never given a basis holds zeros: no column, no cost)
+            sC[i] = (bi >= 1 && bi < af) ? cost[bi - 1] : 0.0;
+        }
+        __syncthreads();
+        batch_objective_big_m<false>(T, tp, m, ncols, sC, cost, af, tid);
+        __syncthreads();
+        pst = RUNNING;                            // lpo_set_objective
+        phase = PH_LOOP1;
+        work = 1;
+    }
+    // lpo_solve over columns 1..N, priced on both rows
+    for (;;) {
+        const int64_t k = batch_price_big_m<RULE>(T + m * tp, T + (m + 1) * tp, ncols - 1, g.eps_opt, tid);   // also the final peek
+        if (k < 0) {
+            status = OPTIMAL;
+            break;
+        }
+        if (budget == 0) {
+            status = ITER_LIMIT;
+            break;
+        }
+        if (work >= chunk) break;
+        const Cand cb = batch_ratio<RULE, TIER>(T, tp, m, k, sB, gB, g.eps_piv, tid);
+        const int64_t r = cb.row;
+        if (r < 0) {
+            status = UNBOUNDED;
+            break;
+        }
+        if (!isfinite(cb.piv) || !isfinite(T[r * tp])) {
+            status = NUMERIC;
+            break;
+        }
+        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, cb.piv, tid, tx, ty, j0, i0);
+        if (tid == 0) {
+            gB[r] = k;
+            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
+            if (g.logk && pivots < g.logcap) {
+                g.logk[b * g.logcap + pivots] = (int32_t)k;
+                g.logr[b * g.logcap + pivots] = (int32_t)r;
+            }
+        }
+        last_k = k;
+        last_r = r;
+        pivots++;
+        budget--;
+        work++;
+        __syncthreads();
+    }
+    if (status != RUNNING && status != ITER_LIMIT) pst = status;   // lpo_ctx.status
+    if (status == OPTIMAL || status == UNBOUNDED) {
+        // artificials still positive: every thread adds the same column in row order
+        double bsum = 0;
+        for (int64_t i = 0; i < m; i++) bsum += fabs(T[i * tp]);
+        if (T[m * tp] < -1e-9 * (bsum > 1.0 ? bsum : 1.0)) status = INFEASIBLE;
+    }
+
+    // store the state
+    if (TIER == TIER_LDS && work > 0) {
+        for (int64_t i = i0; i < rows; i += ty)
+            for (int64_t j = j0; j < ncols; j += tx) gT[i * g.ld + j] = T[i * tp + j];
+    }
+    if (tid == 0) {
+        lp->status = status;
+        lp->pstatus = pst;
+        lp->pivots = pivots;
+        lp->last_k = last_k;
+        lp->last_r = last_r;
+        lp->budget = budget;
+        lp->objective = T[(m + 1) * tp];
+        lp->phase = phase;
+        if (status == RUNNING) atomicAdd(g.running, 1);
+    }
+}
+
 // lpo_set_objective on every LP, costs as k_batch_two_phase's (count x N)
 __global__ __launch_bounds__(kBlock) void k_batch_set_objective(BatchGeo g, const double *costs) {
     const int64_t b = blockIdx.x, m = g.m;
@@ -572,6 +743,7 @@ using namespace lpg;
 struct lpg_batch {
     int device = 0;
     int64_t count = 0, m = 0, ncols = 0, ld = 0, nact = 0;
+    int nobj = 1;                 // 2: a Big-M batch (lpg_batch_create_big_m), tableaus of m + 2 rows
     uint32_t flags = 0;
     double eps_piv = 1e-9, eps_opt = 1e-9;
     int tier = TIER_LDS;
@@ -586,7 +758,7 @@ struct lpg_batch {
     int32_t *logk = nullptr, *logr = nullptr;
     int32_t *running = nullptr;
     unsigned long long *bad = nullptr;
-    double *cost = nullptr;       // count x N real costs of two-phase calls / set_objective (allocated on first use)
+    double *cost = nullptr;       // count x N real costs of two-phase and Big-M calls / set_objective (allocated on first use)
     hipStream_t stream = nullptr;
     char err[512] = {0};
 };
@@ -633,12 +805,13 @@ BatchGeo bgeo(const lpg_batch *b) {
     g.chunk = b->chunk;
     g.pitch = b->pitch;
     g.txs = b->txs;
+    g.nobj = b->nobj;
     return g;
 }
 
-// dynamic LDS of one workgroup: [tableau at an odd pitch] P C [int32 basis]
-int64_t lds_bytes(int tier, int64_t m, int64_t ncols) {
-    const int64_t rows = m + 1, pitch = ncols | 1;
+// dynamic LDS of one workgroup: [tableau of m + nobj rows at an odd pitch] P C [int32 basis]
+int64_t lds_bytes(int tier, int64_t m, int64_t ncols, int nobj) {
+    const int64_t rows = m + nobj, pitch = ncols | 1;
     int64_t d = ncols + rows;
     if (tier == TIER_LDS) d += rows * pitch + (m + 1) / 2;
     return d * (int64_t)sizeof(double);
@@ -696,27 +869,45 @@ int launch_solve(lpg_batch *b, int mode) {
     }
 }
 
-template <int RULE, int TIER>
-int launch_two_phase_t(lpg_batch *b, const TwoPhase &t) {
+// one launch of K = k_batch_two_phase<RULE, TIER> or k_batch_big_m<RULE, TIER> (`name` for the error message)
+template <void (*K)(BatchGeo, TwoPhase)>
+int launch_art_t(lpg_batch *b, const TwoPhase &t, const char *name) {
     static std::atomic<unsigned long long> attr{0};
     const int dev = b->device & 63;
     if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute((const void *)k_batch_two_phase<RULE, TIER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kBatchMaxLds) != hipSuccess) {
+        if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, kBatchMaxLds) != hipSuccess) {
             (void)hipGetLastError();
-            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(k_batch_two_phase, %d bytes of LDS) failed", kBatchMaxLds);
+            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(%s, %d bytes of LDS) failed", name, kBatchMaxLds);
         }
         attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
     }
-    hipLaunchKernelGGL((k_batch_two_phase<RULE, TIER>), dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream,
-                       bgeo(b), t);
+    hipLaunchKernelGGL(K, dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream, bgeo(b), t);
     return 0;
 }
 
 int launch_two_phase(lpg_batch *b, int rule, const TwoPhase &t) {
     const bool l = b->tier == TIER_LDS;
-    if (rule == RULE_BLAND) return l ? launch_two_phase_t<RULE_BLAND, TIER_LDS>(b, t) : launch_two_phase_t<RULE_BLAND, TIER_GLOBAL>(b, t);
-    return l ? launch_two_phase_t<RULE_DANTZIG, TIER_LDS>(b, t) : launch_two_phase_t<RULE_DANTZIG, TIER_GLOBAL>(b, t);
+    const char *n = "k_batch_two_phase";
+    if (rule == RULE_BLAND)
+        return l ? launch_art_t<k_batch_two_phase<RULE_BLAND, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_two_phase<RULE_BLAND, TIER_GLOBAL>>(b, t, n);
+    return l ? launch_art_t<k_batch_two_phase<RULE_DANTZIG, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_two_phase<RULE_DANTZIG, TIER_GLOBAL>>(b, t, n);
+}
+
+int launch_big_m(lpg_batch *b, int rule, const TwoPhase &t) {
+    const bool l = b->tier == TIER_LDS;
+    const char *n = "k_batch_big_m";
+    if (rule == RULE_BLAND)
+        return l ? launch_art_t<k_batch_big_m<RULE_BLAND, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_big_m<RULE_BLAND, TIER_GLOBAL>>(b, t, n);
+    return l ? launch_art_t<k_batch_big_m<RULE_DANTZIG, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_big_m<RULE_DANTZIG, TIER_GLOBAL>>(b, t, n);
+}
+
+// what a Big-M batch refuses (and a plain batch, for lpg_batch_solve_big_m)
+int wrong_kind(lpg_batch *b, const char *call) {
+    if (b->nobj == 2)
+        return bfail(b, LPG_ERR_STATE, "%s: this is a Big-M batch (lpg_batch_create_big_m, two objective rows); only "
+                                       "lpg_batch_solve_big_m pivots it; nothing has pivoted", call);
+    return bfail(b, LPG_ERR_STATE, "%s: the batch has one objective row (lpg_batch_create); Big-M needs a batch from "
+                                   "lpg_batch_create_big_m; nothing has pivoted", call);
 }
 
 // the batch's count x N cost buffer, filled from the host's (pitch ld_cost) when given
@@ -734,7 +925,7 @@ int stage_costs(lpg_batch *b, const double *cost, int64_t ld_cost) {
     return 0;
 }
 
-// two == nullptr: k_batch_solve in `mode`; else k_batch_two_phase with rule `mode`
+// two == nullptr: k_batch_solve in `mode`; else k_batch_two_phase (k_batch_big_m on a Big-M batch) with rule `mode`
 int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const TwoPhase *two = nullptr) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "max_pivots < 0");
@@ -764,10 +955,12 @@ int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const
     // drive-out pivots (at most m) and the two objectives are work as well
     int64_t max_launches = max_pivots / b->chunk + 2;
     if (two) max_launches = 2 * std::min<int64_t>(max_pivots / b->chunk, (int64_t)1 << 60) + (b->m + 2) / b->chunk + 4;
+    if (two && b->nobj == 2) max_launches = max_pivots / b->chunk + 4;     // the pivots and one objective unit
     for (int64_t it = 0;; it++) {
         int32_t running = 0;
         BHIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
-        if (int rc = two ? launch_two_phase(b, mode, *two) : launch_solve(b, mode)) return rc;
+        if (int rc = !two ? launch_solve(b, mode) : b->nobj == 2 ? launch_big_m(b, mode, *two) : launch_two_phase(b, mode, *two))
+            return rc;
         BHIPCHK(b, hipGetLastError());
         BHIPCHK(b, hipMemcpyAsync(&running, b->running, sizeof running, hipMemcpyDeviceToHost, b->stream));
         BHIPCHK(b, hipStreamSynchronize(b->stream));
@@ -791,28 +984,25 @@ int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *lpg_batch_last_error(const lpg_batch *b) { return b ? b->err : g_berr; }
-
-int lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags) {
+// lpg_batch_create (nobj = 1) and lpg_batch_create_big_m (nobj = 2); `call` names the entry point
+int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags, int nobj,
+                 const char *call) {
     if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (count < 1 || m < 1 || ncols < 2)
-        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: bad shape count=%lld m=%lld ncols=%lld (need count >= 1, "
-                                           "m >= 1, ncols >= 2)", (long long)count, (long long)m, (long long)ncols);
+        return bfail(nullptr, LPG_ERR_ARG, "%s: bad shape count=%lld m=%lld ncols=%lld (need count >= 1, "
+                                           "m >= 1, ncols >= 2)", call, (long long)count, (long long)m, (long long)ncols);
     if (flags & ~(uint32_t)LPG_FLAG_NO_LOG)
-        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: flags 0x%x not supported (LPG_FLAG_NO_LOG only: no Big-M, "
-                                           "eager or no-skip batches)", flags);
-    if (m + 1 > LPG_BATCH_MAX_DIM || ncols > LPG_BATCH_MAX_DIM)
-        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: m + 1 = %lld, ncols = %lld exceed %d; a tableau this large "
-                                           "belongs to lpg_create", (long long)(m + 1), (long long)ncols, LPG_BATCH_MAX_DIM);
-    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: device %d", device);
-    const int64_t rows = m + 1, ld = (ncols + 63) & ~(int64_t)63;   // the engine's padded pitch (512-byte rows)
+        return bfail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_FLAG_NO_LOG only: a Big-M batch comes from "
+                                           "lpg_batch_create_big_m; no eager or no-skip batches)", call, flags);
+    if (m + nobj > LPG_BATCH_MAX_DIM || ncols > LPG_BATCH_MAX_DIM)
+        return bfail(nullptr, LPG_ERR_ARG, "%s: m + %d = %lld, ncols = %lld exceed %d; a tableau this large "
+                                           "belongs to lpg_create", call, nobj, (long long)(m + nobj), (long long)ncols,
+                     LPG_BATCH_MAX_DIM);
+    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+    const int64_t rows = m + nobj, ld = (ncols + 63) & ~(int64_t)63;   // the engine's padded pitch (512-byte rows)
     if (count > (int64_t)0x7fffffff / rows)
-        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create: count * (m + 1) = %lld x %lld exceeds 2^31 - 1",
+        return bfail(nullptr, LPG_ERR_ARG, "%s: count * (m + %d) = %lld x %lld exceeds 2^31 - 1", call, nobj,
                      (long long)count, (long long)rows);
     int chunk = 0;
     if (const char *ce = getenv("LPG_BATCH_CHUNK")) {
@@ -828,11 +1018,12 @@ int lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int6
     b->ncols = ncols;
     b->ld = ld;
     b->nact = ncols - 1;
+    b->nobj = nobj;
     b->flags = flags;
     const char *te = getenv("LPG_BATCH_TIER");
     const bool force_global = te && !strcmp(te, "global");
-    b->tier = (!force_global && lds_bytes(TIER_LDS, m, ncols) <= kBatchMaxLds) ? TIER_LDS : TIER_GLOBAL;
-    b->lds = lds_bytes(b->tier, m, ncols);
+    b->tier = (!force_global && lds_bytes(TIER_LDS, m, ncols, nobj) <= kBatchMaxLds) ? TIER_LDS : TIER_GLOBAL;
+    b->lds = lds_bytes(b->tier, m, ncols, nobj);
     b->pitch = (int)(ncols | 1);
     while ((1 << b->txs) < ncols && b->txs < 8) b->txs++;
     if (!chunk) {
@@ -888,6 +1079,20 @@ int lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int6
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+const char *lpg_batch_last_error(const lpg_batch *b) { return b ? b->err : g_berr; }
+
+int lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags) {
+    return batch_create(out, device, count, m, ncols, flags, 1, "lpg_batch_create");
+}
+
+int lpg_batch_create_big_m(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags) {
+    return batch_create(out, device, count, m, ncols, flags, 2, "lpg_batch_create_big_m");
+}
+
 void lpg_batch_destroy(lpg_batch *b) {
     if (!b) return;
     if (b->T || b->stream) (void)hipSetDevice(b->device);
@@ -916,6 +1121,8 @@ int lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *o) {
     o->chunk = b->chunk;
     o->lds_bytes = b->lds;
     o->log_capacity = b->logcap;
+    o->nobj = b->nobj;
+    o->pad = 0;
     return 0;
 }
 
@@ -930,8 +1137,8 @@ int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableau
                              (long long)(q % b->m), (long long)(first + q / b->m), (long long)(b->ncols - 1));
     if (n == 0) return 0;
     BHIPCHK(b, hipSetDevice(b->device));
-    const int64_t rows = b->m + 1;
-    // rows are back to back on both sides: one strided copy of n * (m + 1) rows
+    const int64_t rows = b->m + b->nobj;
+    // rows are back to back on both sides: one strided copy of n * (m + nobj) rows
     BHIPCHK(b, hipMemcpy2DAsync(b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double), tableaus,
                                 (size_t)ld * sizeof(double), (size_t)b->ncols * sizeof(double), (size_t)(n * rows),
                                 hipMemcpyHostToDevice, b->stream));
@@ -947,6 +1154,7 @@ int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableau
 
 int lpg_batch_generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_generate");
     if (n < 1 || b->ncols != n + b->m + 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
                      (long long)(n + b->m + 1));
@@ -970,6 +1178,7 @@ int lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt) {
 }
 
 int lpg_batch_set_active_columns(lpg_batch *b, int64_t nact) {
+    if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_set_active_columns");
     if (!b || nact < 1 || nact > b->ncols - 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_set_active_columns: nact out of range 1..N");
     b->nact = nact;
@@ -987,17 +1196,20 @@ int lpg_batch_reserve_log(lpg_batch *b, int64_t npivots) {
 }
 
 int lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out) {
+    if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_solve");
     if (b && rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve: rule %d", rule);
     return batch_run(b, max_pivots, rule, out);
 }
 
 int lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out) {
+    if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_solve_dual");
     return batch_run(b, max_pivots, MODE_DUAL, out);
 }
 
 int lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
                               int rule, lpg_result *out) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_solve_two_phase");
     const int64_t N = b->ncols - 1;
     if (art_first < 2 || art_first > N)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: art_first %lld outside 2..%lld", (long long)art_first,
@@ -1018,8 +1230,32 @@ int lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cos
     return batch_run(b, max_pivots, rule, out, &t);
 }
 
+int lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
+                          int rule, lpg_result *out) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (b->nobj != 2) return wrong_kind(b, "lpg_batch_solve_big_m");
+    const int64_t N = b->ncols - 1;
+    if (art_first < 2 || art_first > N)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: art_first %lld outside 2..%lld", (long long)art_first,
+                     (long long)N);
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: rule %d", rule);
+    if (cost && ld_cost < N)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: ld_cost %lld < N = %lld", (long long)ld_cost, (long long)N);
+    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: max_pivots < 0");
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
+    TwoPhase t{};
+    t.cost = b->cost;
+    t.art_first = art_first;
+    t.max_pivots = max_pivots;
+    t.save_cost = cost ? 0 : 1;
+    return batch_run(b, max_pivots, rule, out, &t);     // all columns 1..N are priced: nact stays N
+}
+
 int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
     if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: NULL argument");
+    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_set_objective");
     if (ld_cost < b->ncols - 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: ld_cost %lld < N = %lld", (long long)ld_cost,
                      (long long)(b->ncols - 1));
@@ -1037,8 +1273,8 @@ int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate_artificial: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
                      (long long)(n + b->m + 1));
     BHIPCHK(b, hipSetDevice(b->device));
-    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + 1))), dim3(kBlock), 0, b->stream, bgeo(b), n,
-                       seed, (int)LPG_GEN_ARTIFICIAL);
+    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + b->nobj))), dim3(kBlock), 0, b->stream, bgeo(b),
+                       n, seed, (int)LPG_GEN_ARTIFICIAL);
     hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
     BHIPCHK(b, hipGetLastError());
     BHIPCHK(b, hipStreamSynchronize(b->stream));
@@ -1053,7 +1289,7 @@ int lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int6
     if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
     if (n == 0) return 0;
     BHIPCHK(b, hipSetDevice(b->device));
-    const int64_t rows = b->m + 1;
+    const int64_t rows = b->m + b->nobj;
     BHIPCHK(b, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double),
                                 (size_t)b->ncols * sizeof(double), (size_t)(n * rows), hipMemcpyDeviceToHost, b->stream));
     BHIPCHK(b, hipStreamSynchronize(b->stream));

@@ -293,15 +293,18 @@ class Engine:
 
 class BatchEngine:
     """`count` LPs of one shape, each an (m+1) x ncols tableau, solved in one
-    launch with one workgroup per LP (include/lpg.h, "batches")."""
+    launch with one workgroup per LP (include/lpg.h, "batches"). ``big_m=True``:
+    a Big-M batch, (m+2) x ncols tableaus (row m the M part, row m + 1 the real
+    part of the objective), solved by solve_big_m only."""
 
-    def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None):
+    def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None, big_m: bool = False):
         self.lib = lib if lib is not None else L.load()
         self._b = ctypes.c_void_p()
-        rc = self.lib.lpg_batch_create(ctypes.byref(self._b), device, count, m, ncols, flags)
+        name = "lpg_batch_create_big_m" if big_m else "lpg_batch_create"
+        rc = getattr(self.lib, name)(ctypes.byref(self._b), device, count, m, ncols, flags)
         if rc != 0:
-            raise LPGError(f"lpg_batch_create rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
-        self.count, self.m, self.ncols = count, m, ncols
+            raise LPGError(f"{name} rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+        self.count, self.m, self.ncols, self.nobj = count, m, ncols, 2 if big_m else 1
 
     def close(self):
         if self._b:
@@ -333,10 +336,11 @@ class BatchEngine:
 
     # -- loading ---------------------------------------------------------
     def load(self, T: np.ndarray, basis=None, first: int = 0):
-        """T: [n, m+1, ncols] tableaus (objective row last), basis: [n, m]; LPs first .. first + n - 1."""
+        """T: [n, m+1, ncols] tableaus (objective row last; Big-M batch: [n, m+2, ncols], M part then real part),
+        basis: [n, m]; LPs first .. first + n - 1."""
         T = np.ascontiguousarray(T, dtype=np.float64)
-        if T.ndim != 3 or T.shape[1] != self.m + 1 or T.shape[2] != self.ncols:
-            raise LPGError(f"load: tableaus of shape {T.shape}, want [n, {self.m + 1}, {self.ncols}]")
+        if T.ndim != 3 or T.shape[1] != self.m + self.nobj or T.shape[2] != self.ncols:
+            raise LPGError(f"load: tableaus of shape {T.shape}, want [n, {self.m + self.nobj}, {self.ncols}]")
         bp = None
         if basis is not None:
             basis = np.ascontiguousarray(basis, dtype=np.int64)
@@ -390,6 +394,16 @@ class BatchEngine:
         del keep
         return [_res(x) for x in r]
 
+    def solve_big_m(self, art_first: int, cost=None, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> list:
+        """Engine.solve_big_m on every LP of a Big-M batch in one launch; cost as solve_two_phase's.
+        Another call goes on where a budget-limited one stopped."""
+        keep, cp, ld = (None, None, 0) if cost is None else self._costs(cost, "solve_big_m")
+        r = (L.Result * self.count)()
+        self._check(self.lib.lpg_batch_solve_big_m(self._b, art_first, cp, ld, max_pivots, rule, r),
+                    "lpg_batch_solve_big_m")
+        del keep
+        return [_res(x) for x in r]
+
     def set_objective(self, cost):
         """Engine.set_objective on every LP; cost: [N] or [count, >= N]."""
         keep, cp, ld = self._costs(cost, "set_objective")
@@ -406,7 +420,7 @@ class BatchEngine:
     # -- readout ---------------------------------------------------------
     def get_rows(self, first: int = 0, n: int = None) -> np.ndarray:
         n = self.count - first if n is None else n
-        out = np.zeros((n, self.m + 1, self.ncols), dtype=np.float64)
+        out = np.zeros((n, self.m + self.nobj, self.ncols), dtype=np.float64)
         self._check(self.lib.lpg_batch_get_rows(self._b, first, n, out.ctypes.data_as(L.c_double_p), self.ncols),
                     "lpg_batch_get_rows")
         return out

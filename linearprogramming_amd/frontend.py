@@ -710,31 +710,53 @@ def _groups(arrays) -> dict:
     return groups
 
 
-def solve_batch(sms, rule=None, device: int = 0) -> list:
-    """solve(sm) for every SMatrix of ``sms`` (two-phase where rows lack a basic
-    column, the plain primal simplex where none does), the models of one shape
-    (m, nc0, nlack) together in one BatchEngine: one launch per group instead
-    of one engine per model. The result list is in input order and each entry
-    equals solve(sm) field by field, floats bit for bit."""
+def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase") -> list:
+    """solve(sm, method=method) for every SMatrix of ``sms``, the models of one
+    shape (m, nc0, nlack) together in one BatchEngine: one launch per group
+    instead of one engine per model. ``method`` as solve()'s: "two_phase" or
+    "big_m" where rows lack a basic column (the plain primal simplex where none
+    does), or "dual" (every model must pass solve()'s two checks: no row without
+    a slack basis, no positive max-form cost; the FrontendError names the first
+    offending model and no device work has started). Unlike solve(), which takes
+    an unknown method for "two_phase", any other method is a FrontendError: a
+    misspelt method would otherwise cost a whole batch. The result list is in
+    input order and each entry equals solve(sm, method=method) field by field,
+    floats bit for bit."""
     from . import _lib as L
     from .engine import BatchEngine
+    if method not in ("two_phase", "big_m", "dual"):
+        raise FrontendError(f"solve_batch: unknown method {method!r}")
     if rule is None:
         rule = L.RULE_DANTZIG
     sms = list(sms)
     arrays = [engine_arrays(sm) for sm in sms]
+    if method == "dual":
+        for idx, sm in enumerate(sms):
+            if arrays[idx][4]:
+                raise FrontendError(f"dual simplex: model {idx} has rows without a slack basis (equality rows); use "
+                                    "build_smatrix(text, dual=True)")
+            if any(_dec(c) > 0 for c in sm.costs):
+                raise FrontendError(f"dual simplex: the slack basis of model {idx} is not dual feasible (a positive "
+                                    "max-form cost)")
     out = [None] * len(sms)
     for (m, nc0, nlack), members in _groups(arrays).items():
         nc = nc0 + nlack
-        T = np.zeros((len(members), m + 1, nc), dtype=np.float64)
+        bigm = method == "big_m" and nlack > 0
+        T = np.zeros((len(members), m + (2 if bigm else 1), nc), dtype=np.float64)
         for q, idx in enumerate(members):
             T[q, :m] = arrays[idx][0]
         basis = np.array([arrays[idx][1] for idx in members], dtype=np.int64)
         cost = np.array([arrays[idx][2] for idx in members], dtype=np.float64)
-        with BatchEngine(len(members), m, nc, device=device) as e:
+        with BatchEngine(len(members), m, nc, device=device, big_m=bigm) as e:
             e.load(T, basis)
-            if nlack == 0:
+            if method == "dual":
+                e.set_objective(cost)
+                res, used = e.solve_dual(), "dual"
+            elif nlack == 0:
                 e.set_objective(cost)
                 res, used = e.solve(rule=rule), "primal"
+            elif bigm:
+                res, used = e.solve_big_m(nc0, cost, rule=rule), "big_m"
             else:
                 res, used = e.solve_two_phase(nc0, cost, rule=rule), "two_phase"
             rows, bas = e.get_rows(), e.get_basis()

@@ -6,7 +6,10 @@
 --kind artificial: the generator's artificial LPs (equality rows with
 artificial unit columns) by the two-phase method, (a) generate_artificial +
 BatchEngine.solve_two_phase, (b) generate(kind=GEN_ARTIFICIAL) +
-Engine.solve_two_phase per LP.
+Engine.solve_two_phase per LP. With --method big_m (valid with --kind
+artificial): (a) a Big-M BatchEngine, generate_artificial + solve_big_m, (b)
+Engine(flags=FLAG_BIG_M), generate(kind=GEN_ARTIFICIAL), solve_big_m, close
+per LP.
 
 (a) one BatchEngine.solve over B LPs (seeds S, S + 1, ...): generate (not
     timed), then the wall time of solve(), which returns after a device
@@ -50,6 +53,8 @@ def main() -> int:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=20220518)
     ap.add_argument("--kind", choices=sorted(KINDS), default="dense")
+    ap.add_argument("--method", choices=["two_phase", "big_m"], default="two_phase",
+                    help="how --kind artificial is solved (big_m: Big-M batch vs a loop of FLAG_BIG_M engines)")
     ap.add_argument("--rule", choices=["dantzig", "bland"], default="dantzig")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-loop", action="store_true", help="time (a) only (e.g. to compare the tiers: LPG_BATCH_TIER=global)")
@@ -61,16 +66,19 @@ def main() -> int:
     kind, rule = KINDS[a.kind], 1 if a.rule == "bland" else 0
     budget = 50 * (m + n)
     two = a.kind == "artificial"
+    bigm = a.method == "big_m"
+    if bigm and not two:
+        ap.error("--method big_m needs --kind artificial")
     cus = 256
 
-    be = lpg.BatchEngine(B, m, nc, device=a.device, flags=lpg._lib.FLAG_NO_LOG)
+    be = lpg.BatchEngine(B, m, nc, device=a.device, flags=lpg._lib.FLAG_NO_LOG, big_m=bigm)
     info = be.info
 
     def run_batch():
         if two:
             af = be.generate_artificial(n, a.seed)
             t0 = time.perf_counter()
-            res = be.solve_two_phase(af, None, budget, rule)
+            res = be.solve_big_m(af, None, budget, rule) if bigm else be.solve_two_phase(af, None, budget, rule)
         else:
             be.generate(n, a.seed, kind)
             t0 = time.perf_counter()
@@ -81,9 +89,12 @@ def main() -> int:
         out = []
         t0 = time.perf_counter()
         for b in range(B):
-            e = lpg.Engine(m, nc, device=a.device, flags=lpg._lib.FLAG_NO_LOG)
+            e = lpg.Engine(m, nc, device=a.device, flags=lpg._lib.FLAG_NO_LOG | (lpg._lib.FLAG_BIG_M if bigm else 0))
             e.generate(n, a.seed + b, kind)
-            r = e.solve_two_phase(1 + n + (m + 1) // 2, None, budget, rule) if two else e.solve(budget, rule)   # synchronises
+            if bigm:
+                r = e.solve_big_m(1 + n + (m + 1) // 2, None, budget, rule)
+            else:
+                r = e.solve_two_phase(1 + n + (m + 1) // 2, None, budget, rule) if two else e.solve(budget, rule)   # synchronises
             out.append((r.status, r.pivots))
             e.close()
         return time.perf_counter() - t0, out
@@ -124,6 +135,7 @@ def main() -> int:
     resident = max(1, min(B, cus * min(8, max(1, (160 * 1024) // (int(info.lds_bytes) + 512)))))
     line = {
         "bench": "batch_vs_loop", "m": m, "n": n, "ncols": nc, "batch": B, "kind": a.kind, "rule": a.rule,
+        "method": ("big_m" if bigm else "two_phase") if two else "primal",
         "tier": "lds" if info.tier == lpg.BATCH_TIER_LDS else "global", "lds_bytes": int(info.lds_bytes),
         "chunk": int(info.chunk), "repeats": a.repeats, "statuses": statuses, "pivots": pivots,
         "batch_solve": ra,
@@ -140,7 +152,7 @@ def main() -> int:
             "us_per_pivot_chip_loop": rb["seconds_median"] * 1e6 / pivots,
         })
     if info.tier == lpg.BATCH_TIER_LDS:
-        bytes_each_way = (m + 1) * nc * 8
+        bytes_each_way = (m + int(info.nobj)) * nc * 8
         line["lds_model_us_per_pivot"] = (bytes_each_way / DS_READ_B64_BPC + bytes_each_way / DS_WRITE_B64_BPC) / CLK_HZ * 1e6
     text = json.dumps(line)
     print(text)

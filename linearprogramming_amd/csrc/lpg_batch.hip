@@ -27,6 +27,11 @@
 // Big-M batches (lpg_batch_create_big_m) carry two objective rows per LP, the
 // M part in row m and the real part in row m + 1, and are solved by
 // k_batch_big_m with lexicographic pricing (lpo.c lpo_solve_big_m).
+//
+// The three solve kernels (k_batch_solve, k_batch_two_phase, k_batch_big_m)
+// are their method's state machine over one set of parts: BatchView (where
+// the LP lives, load / store, apply a pivot), batch_primal_step (one step of
+// lpo_solve), batch_objective (an objective row) and batch_write_back.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -56,7 +61,7 @@ struct BatchLP {              // 64 B of state per LP
     int64_t pivots;
     int64_t last_k, last_r;
     int64_t budget;           // pivots the current solve call may still apply
-    double  objective;        // T[m][0] after the last launch
+    double  objective;        // the (real) objective row's column 0 after the last launch
     int32_t phase;            // two-phase, Big-M: where the LP stands (PH_*); round-trips between launches
     int32_t pad;
     int64_t cursor;           // two-phase: the next row the drive-out looks at
@@ -153,6 +158,16 @@ __global__ void k_batch_begin(BatchLP *lp, int64_t count, int64_t budget, int du
     lp[q].status = dual ? RUNNING : lp[q].pstatus;
 }
 
+// a two-phase or Big-M call begins: every LP starts at PH_OBJ1 again, whatever its status
+__global__ void k_batch_begin_two_phase(BatchLP *lp, int64_t count, int64_t budget) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= count) return;
+    lp[q].budget = budget;
+    lp[q].status = RUNNING;
+    lp[q].phase = PH_OBJ1;
+    lp[q].cursor = 0;
+}
+
 // dual feasibility of every LP: bad[0] = the first LP with a d_j < -eps_opt
 __global__ __launch_bounds__(kBlock) void k_batch_dual_check(BatchGeo g, unsigned long long *bad) {
     const int64_t b = blockIdx.x;
@@ -163,9 +178,121 @@ __global__ __launch_bounds__(kBlock) void k_batch_dual_check(BatchGeo g, unsigne
 }
 
 // ------------------------------------------------------------------------
-// the steps of one pivot, shared by k_batch_solve and k_batch_two_phase
-// (whole-block calls from uniform control flow; results uniform)
+// the parts the three solve kernels are made of (whole-block calls from
+// uniform control flow; results uniform)
 // ------------------------------------------------------------------------
+
+// lpo_pivot's arithmetic on (k, r) with pivot element piv; the caller records
+// the basis and the log and puts a barrier behind them
+__device__ __forceinline__ void batch_pivot(double *T, int64_t tp, int64_t rows, int64_t ncols, double *sP, double *sC,
+                                            int64_t k, int64_t r, double piv, int tid, int tx, int ty, int j0, int i0) {
+    // P, C
+    for (int64_t j = tid; j < ncols; j += kBlock) sP[j] = T[r * tp + j] / piv;
+    for (int64_t i = tid; i < rows; i += kBlock) sC[i] = T[i * tp + k];
+    __syncthreads();
+    // rank-1 update (lpo_pivot)
+    // a thread keeps its column's P[j] and walks the rows four at a time:
+    // the four loads are issued before the first store, so their latencies
+    // overlap (the compiler cannot reorder them itself: T, P and C may alias)
+    for (int64_t j = j0; j < ncols; j += tx) {
+        const double pj = sP[j];
+        double *col = T + j;
+        int64_t i = i0;
+        for (; i + 3 * ty < rows; i += 4 * ty) {
+            double c[4], t[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                c[u] = sC[i + u * ty];
+                t[u] = col[(i + u * ty) * tp];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) col[(i + u * ty) * tp] = (i + u * ty == r) ? pj : fma(-c[u], pj, t[u]);
+        }
+        for (; i < rows; i += ty) col[i * tp] = (i == r) ? pj : fma(-sC[i], pj, col[i * tp]);
+    }
+}
+
+// The LP of this workgroup: where its tableau and basis are worked on during
+// the launch, and the moves every method makes on them. `rows` = m + nobj.
+// LDS: [tableau (TIER_LDS)] P[ncols] C[rows] [basis as int32 (TIER_LDS)]
+template <int TIER>
+struct BatchView {
+    double *T, *gT;           // the tableau of the launch (LDS or gT), the LP's tableau in device memory
+    int64_t tp, ld;           // their row pitches
+    int64_t *gB;              // the basis in device memory
+    int32_t *sB;              // TIER_LDS: its mirror
+    double *sP, *sC;
+    int32_t *logk, *logr;     // the LP's log, or null
+    int64_t logcap, m, rows, ncols;
+    int tid, tx, ty, j0, i0;  // update tile coordinates (BatchGeo::txs)
+
+    static __device__ __forceinline__ BatchView make(const BatchGeo &g, int64_t rows) {
+        extern __shared__ double smem[];
+        const int64_t b = blockIdx.x;
+        BatchView v;
+        v.gT = g.T + b * rows * g.ld;
+        v.ld = g.ld;
+        v.tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
+        v.T = TIER == TIER_LDS ? smem : v.gT;
+        v.gB = g.basis + b * g.m;
+        v.sP = TIER == TIER_LDS ? smem + rows * v.tp : smem;
+        v.sC = v.sP + g.ncols;
+        v.sB = (int32_t *)(v.sC + rows);
+        v.logk = g.logk ? g.logk + b * g.logcap : nullptr;
+        v.logr = g.logk ? g.logr + b * g.logcap : nullptr;
+        v.logcap = g.logcap;
+        v.m = g.m;
+        v.rows = rows;
+        v.ncols = g.ncols;
+        v.tid = threadIdx.x;
+        v.tx = 1 << g.txs;
+        v.ty = kBlock >> g.txs;
+        v.j0 = v.tid & (v.tx - 1);
+        v.i0 = v.tid >> g.txs;
+        return v;
+    }
+
+    __device__ __forceinline__ void load() const {
+        if (TIER == TIER_LDS) {
+            for (int64_t i = i0; i < rows; i += ty)
+                for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * ld + j];
+            for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
+        }
+        __syncthreads();
+    }
+
+    // the tableau back to device memory, where the launch changed it
+    __device__ __forceinline__ void store(bool worked) const {
+        if (TIER == TIER_LDS && worked) {
+            for (int64_t i = i0; i < rows; i += ty)
+                for (int64_t j = j0; j < ncols; j += tx) gT[i * ld + j] = T[i * tp + j];
+        }
+    }
+
+    __device__ __forceinline__ int64_t basis(int64_t i) const { return TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]; }
+
+    // (k, r) with pivot element piv: the update, the basis, its mirror, entry `q` of the log
+    __device__ __forceinline__ void apply(int64_t k, int64_t r, double piv, int64_t q) const {
+        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, piv, tid, tx, ty, j0, i0);
+        if (tid == 0) {
+            gB[r] = k;
+            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
+            if (logk && q < logcap) {
+                logk[q] = (int32_t)k;
+                logr[q] = (int32_t)r;
+            }
+        }
+        __syncthreads();
+    }
+
+    // the phase-I / M objective says artificials are still positive (lpo.c's
+    // feasibility test); every thread adds the same column in row order
+    __device__ __forceinline__ bool artificials_positive() const {
+        double bsum = 0;
+        for (int64_t i = 0; i < m; i++) bsum += fabs(T[i * tp]);
+        return T[m * tp] < -1e-9 * (bsum > 1.0 ? bsum : 1.0);
+    }
+};
 
 // pricing over columns 1..nact of the objective row (lpo.c price): the entering column or -1
 template <int RULE>
@@ -200,195 +327,168 @@ __device__ __forceinline__ int64_t batch_price_big_m(const double *objM, const d
 
 // ratio test of column k (lpo.c ratio_block, cand_less): row < 0 when there is none
 template <int RULE, int TIER>
-__device__ __forceinline__ Cand batch_ratio(const double *T, int64_t tp, int64_t m, int64_t k, const int32_t *sB,
-                                            const int64_t *gB, double eps_piv, int tid) {
+__device__ __forceinline__ Cand batch_ratio(const BatchView<TIER> &v, int64_t k, double eps_piv) {
     Cand cb{0.0, 0.0, 0, -1};
-    for (int64_t i = tid; i < m; i += kBlock) {
-        const double a = T[i * tp + k], bi = T[i * tp];
+    for (int64_t i = v.tid; i < v.m; i += kBlock) {
+        const double a = v.T[i * v.tp + k], bi = v.T[i * v.tp];
         Cand c;
         c.theta = bi > 0.0 ? bi / a : 0.0;
         c.piv = a;
-        c.key = RULE == RULE_BLAND ? (TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]) : i;
+        c.key = RULE == RULE_BLAND ? v.basis(i) : i;
         c.row = a > eps_piv ? i : -1;
         cand_take(cb, c, cand_better(c, cb));
     }
     return block_argmin_cand(cb);
 }
 
-// lpo_pivot's arithmetic on (k, r) with pivot element piv; the caller records
-// the basis and the log and puts a barrier behind them
-__device__ __forceinline__ void batch_pivot(double *T, int64_t tp, int64_t rows, int64_t ncols, double *sP, double *sC,
-                                            int64_t k, int64_t r, double piv, int tid, int tx, int ty, int j0, int i0) {
-    // P, C
-    for (int64_t j = tid; j < ncols; j += kBlock) sP[j] = T[r * tp + j] / piv;
-    for (int64_t i = tid; i < rows; i += kBlock) sC[i] = T[i * tp + k];
-    __syncthreads();
-    // rank-1 update (lpo_pivot)
-    // a thread keeps its column's P[j] and walks the rows four at a time:
-    // the four loads are issued before the first store, so their latencies
-    // overlap (the compiler cannot reorder them itself: T, P and C may alias)
-    for (int64_t j = j0; j < ncols; j += tx) {
-        const double pj = sP[j];
-        double *col = T + j;
-        int64_t i = i0;
-        for (; i + 3 * ty < rows; i += 4 * ty) {
-            double c[4], t[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                c[u] = sC[i + u * ty];
-                t[u] = col[(i + u * ty) * tp];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) col[(i + u * ty) * tp] = (i + u * ty == r) ? pj : fma(-c[u], pj, t[u]);
-        }
-        for (; i < rows; i += ty) col[i * tp] = (i == r) ? pj : fma(-sC[i], pj, col[i * tp]);
-    }
+// What a step of a pivot loop returns: STEP_APPLIED (a pivot was applied and
+// (k, r) set), RUNNING (the launch's work is spent: the loop goes on in the
+// next launch), or the loop's final status.
+constexpr int32_t STEP_APPLIED = -1;
+
+// One step of lpo_solve. price() gives the entering column and is also the
+// final peek when the budget is spent; `budget` pivots are left to the call
+// and `room` units of work to the launch; the pivot becomes entry `q` of the
+// log. The order of the checks is the oracle's.
+template <int RULE, int TIER, class Price>
+__device__ __forceinline__ int32_t batch_primal_step(const BatchView<TIER> &v, Price price, double eps_piv, int64_t budget,
+                                                     int64_t room, int64_t q, int64_t &k, int64_t &r) {
+    const int64_t kk = price();
+    if (kk < 0) return OPTIMAL;
+    if (budget == 0) return ITER_LIMIT;
+    if (room <= 0) return RUNNING;
+    const Cand cb = batch_ratio<RULE, TIER>(v, kk, eps_piv);
+    if (cb.row < 0) return UNBOUNDED;
+    if (!isfinite(cb.piv) || !isfinite(v.T[cb.row * v.tp])) return NUMERIC;
+    v.apply(kk, cb.row, cb.piv, q);
+    k = kk;
+    r = cb.row;
+    return STEP_APPLIED;
 }
 
-// lpo.c set_objective_row: d_j = sum_i c_B(i) T[i][j] - c_j, per column one
-// fma chain over the rows in order (lane = column: conflict-free in LDS,
-// coalesced in device memory; rows are never reduced across lanes). cB[i]
-// holds c_B(i); PHASE1: c_j = -1 from art_first on and 0 before, else cost[j-1].
-template <bool PHASE1>
-__device__ __forceinline__ void batch_objective(double *T, int64_t tp, int64_t m, int64_t ncols, const double *cB,
-                                                const double *cost, int64_t art_first, int tid) {
-    for (int64_t j = tid; j < ncols; j += kBlock) {
+// One step of lpo_solve_dual on the objective row m, arguments as batch_primal_step's
+template <int TIER>
+__device__ __forceinline__ int32_t batch_dual_step(const BatchView<TIER> &v, int64_t nact, double eps_piv, double eps_opt,
+                                                   int64_t budget, int64_t room, int64_t q, int64_t &k, int64_t &r) {
+    // leaving row: most negative b_i, ties -> smallest row
+    PricePart pb{0.0, -1, 0, 0};
+    for (int64_t i = v.tid; i < v.m; i += kBlock) {
+        const double bi = v.T[i * v.tp];
+        PricePart c{bi, bi < -eps_opt ? i : -1, 0, (int32_t)i};
+        pp_take(pb, c, pp_better<RULE_DANTZIG>(c, pb));
+    }
+    pb = block_argmin_pp<RULE_DANTZIG>(pb);
+    const int64_t rr = pb.j;
+    if (rr < 0) return OPTIMAL;
+    if (budget == 0) return ITER_LIMIT;
+    if (room <= 0) return RUNNING;
+    // entering column: min d_j / -a_rj over a_rj < -eps_piv, ties -> smallest j
+    Cand cb{0.0, 0.0, 0, -1};
+    for (int64_t j = 1 + v.tid; j <= nact; j += kBlock) {
+        const double a = v.T[rr * v.tp + j], d = v.T[v.m * v.tp + j];
+        Cand c;
+        c.theta = d > 0.0 ? d / -a : 0.0;
+        c.piv = a;
+        c.key = j;
+        c.row = a < -eps_piv ? j : -1;
+        cand_take(cb, c, cand_better(c, cb));
+    }
+    cb = block_argmin_cand(cb);
+    if (cb.row < 0) return INFEASIBLE;
+    v.apply(cb.row, rr, cb.piv, q);
+    k = cb.row;
+    r = rr;
+    return STEP_APPLIED;
+}
+
+// The cost c_j of column j >= 0 (no column, no cost: a batch that was never
+// given a basis holds zeros) under the three rules of lpo.c's objectives
+enum : int {
+    COST_ART,                 // phase I, the Big-M M part: -1 on the artificial columns (art_first on), 0 before
+    COST_REAL,                // phase II: cost[j - 1]
+    COST_REAL_NO_ART,         // the Big-M real part: cost[j - 1], the artificial columns forced to 0
+};
+template <int COST>
+__device__ __forceinline__ double batch_cost(const double *cost, int64_t art_first, int64_t j) {
+    if (COST == COST_ART) return j >= art_first ? -1.0 : 0.0;
+    if (COST == COST_REAL) return j >= 1 ? cost[j - 1] : 0.0;
+    return (j >= 1 && j < art_first) ? cost[j - 1] : 0.0;
+}
+
+// sC[i] = c_B(i), the cost of row i's basic column
+template <int COST, int TIER>
+__device__ __forceinline__ void batch_stage_cb(const BatchView<TIER> &v, const double *cost, int64_t art_first) {
+    for (int64_t i = v.tid; i < v.m; i += kBlock) v.sC[i] = batch_cost<COST>(cost, art_first, v.basis(i));
+    __syncthreads();
+}
+
+// lpo.c set_objective_row into row `row`: d_j = sum_i c_B(i) T[i][j] - c_j,
+// per column one fma chain over the rows 0..m-1 in order (lane = column:
+// conflict-free in LDS, coalesced in device memory; rows are never reduced
+// across lanes)
+template <int COST, int TIER>
+__device__ __forceinline__ void batch_objective(const BatchView<TIER> &v, int64_t row, const double *cost, int64_t art_first) {
+    batch_stage_cb<COST>(v, cost, art_first);
+    const double *cB = v.sC;
+    double *T = v.T;
+    const int64_t tp = v.tp, m = v.m;
+    for (int64_t j = v.tid; j < v.ncols; j += kBlock) {
         double acc = 0.0;
 #pragma unroll 4
         for (int64_t i = 0; i < m; i++) acc = fma(cB[i], T[i * tp + j], acc);
-        if (j > 0) acc = acc - (PHASE1 ? (j >= art_first ? -1.0 : 0.0) : cost[j - 1]);
-        T[m * tp + j] = acc;
+        if (j > 0) acc = acc - batch_cost<COST>(cost, art_first, j);
+        T[row * tp + j] = acc;
     }
+    __syncthreads();
+}
+
+// Thread 0 at the end of a launch: the fields every method owns (phase and
+// cursor are their kernels' own), the objective from the last row, and the
+// count of LPs that go on
+template <int TIER>
+__device__ __forceinline__ void batch_write_back(const BatchGeo &g, const BatchView<TIER> &v, BatchLP *lp, int32_t status,
+                                                 int32_t pstatus, int64_t pivots, int64_t last_k, int64_t last_r,
+                                                 int64_t budget) {
+    lp->status = status;
+    lp->pstatus = pstatus;
+    lp->pivots = pivots;
+    lp->last_k = last_k;
+    lp->last_r = last_r;
+    lp->budget = budget;
+    lp->objective = v.T[(v.rows - 1) * v.tp];
+    if (status == RUNNING) atomicAdd(g.running, 1);
 }
 
 // ------------------------------------------------------------------------
-// the pivot loop of one LP
+// the pivot loop of one LP (lpo.c lpo_solve, lpo_solve_dual)
 // ------------------------------------------------------------------------
 template <int MODE, int TIER>
 __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
-    extern __shared__ double smem[];
-    const int64_t b = blockIdx.x;
-    const int tid = threadIdx.x;
-    BatchLP *lp = g.lp + b;
+    BatchLP *lp = g.lp + blockIdx.x;
     if (lp->status != RUNNING) return;            // finished in an earlier launch (or call): uniform
-    const int64_t m = g.m, rows = m + 1, ncols = g.ncols;
-    double *gT = g.T + b * rows * g.ld;
-    int64_t *gB = g.basis + b * m;
-    // LDS: [tableau (TIER_LDS)] P[ncols] C[rows] [basis as int32 (TIER_LDS)]
-    const int64_t tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
-    double *T = TIER == TIER_LDS ? smem : gT;
-    double *sP = TIER == TIER_LDS ? smem + rows * tp : smem;
-    double *sC = sP + ncols;
-    int32_t *sB = (int32_t *)(sC + rows);
-    const int tx = 1 << g.txs, ty = kBlock >> g.txs;
-    const int j0 = tid & (tx - 1), i0 = tid >> g.txs;
+    const BatchView<TIER> v = BatchView<TIER>::make(g, g.m + 1);
+    int32_t pst = lp->pstatus;
+    int64_t pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
+    v.load();
 
-    const int64_t pivots0 = lp->pivots, budget = lp->budget;
-    int64_t last_k = lp->last_k, last_r = lp->last_r;
-    const int64_t nmax = budget < (int64_t)g.chunk ? budget : (int64_t)g.chunk;
-    if (TIER == TIER_LDS) {
-        for (int64_t i = i0; i < rows; i += ty)
-            for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * g.ld + j];
-        for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
-    }
-    __syncthreads();
-
-    int32_t status = RUNNING;
-    int64_t done = 0;
+    int32_t status;                               // RUNNING where the launch ends in front of a pivot
+    int64_t work = 0;
     for (;;) {
-        int64_t k, r;
-        double piv;
         if constexpr (MODE != MODE_DUAL) {
-            // pricing (lpo.c price): also the final peek when the budget is spent
-            k = batch_price<MODE>(T + m * tp, g.nact, g.eps_opt, tid);
-            if (k < 0) {
-                status = OPTIMAL;
-                break;
-            }
-            if (done == nmax) {
-                if (done == budget) status = ITER_LIMIT;
-                break;
-            }
-            // ratio test (lpo.c ratio_block, cand_less)
-            const Cand cb = batch_ratio<MODE, TIER>(T, tp, m, k, sB, gB, g.eps_piv, tid);
-            r = cb.row;
-            if (r < 0) {
-                status = UNBOUNDED;
-                break;
-            }
-            piv = cb.piv;
-            if (!isfinite(piv) || !isfinite(T[r * tp])) {
-                status = NUMERIC;
-                break;
-            }
+            auto price = [&] { return batch_price<MODE>(v.T + v.m * v.tp, g.nact, g.eps_opt, v.tid); };
+            status = batch_primal_step<MODE>(v, price, g.eps_piv, budget, g.chunk - work, pivots, last_k, last_r);
         } else {
-            // leaving row (lpo_solve_dual): most negative b_i, ties -> smallest row
-            PricePart pb{0.0, -1, 0, 0};
-            for (int64_t i = tid; i < m; i += kBlock) {
-                const double bi = T[i * tp];
-                PricePart c{bi, bi < -g.eps_opt ? i : -1, 0, (int32_t)i};
-                pp_take(pb, c, pp_better<RULE_DANTZIG>(c, pb));
-            }
-            pb = block_argmin_pp<RULE_DANTZIG>(pb);
-            r = pb.j;
-            if (r < 0) {
-                status = OPTIMAL;
-                break;
-            }
-            if (done == nmax) {
-                if (done == budget) status = ITER_LIMIT;
-                break;
-            }
-            // entering column: min d_j / -a_rj over a_rj < -eps_piv, ties -> smallest j
-            Cand cb{0.0, 0.0, 0, -1};
-            for (int64_t j = 1 + tid; j <= g.nact; j += kBlock) {
-                const double a = T[r * tp + j], d = T[m * tp + j];
-                Cand c;
-                c.theta = d > 0.0 ? d / -a : 0.0;
-                c.piv = a;
-                c.key = j;
-                c.row = a < -g.eps_piv ? j : -1;
-                cand_take(cb, c, cand_better(c, cb));
-            }
-            cb = block_argmin_cand(cb);
-            k = cb.row;
-            if (k < 0) {
-                status = INFEASIBLE;
-                break;
-            }
-            piv = cb.piv;
+            status = batch_dual_step(v, g.nact, g.eps_piv, g.eps_opt, budget, g.chunk - work, pivots, last_k, last_r);
         }
-        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, piv, tid, tx, ty, j0, i0);
-        if (tid == 0) {
-            gB[r] = k;
-            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
-            const int64_t q = pivots0 + done;
-            if (g.logk && q < g.logcap) {
-                g.logk[b * g.logcap + q] = (int32_t)k;
-                g.logr[b * g.logcap + q] = (int32_t)r;
-            }
-        }
-        last_k = k;
-        last_r = r;
-        done++;
-        __syncthreads();
+        if (status != STEP_APPLIED) break;
+        pivots++;
+        budget--;
+        work++;
     }
+    if (MODE != MODE_DUAL && status != RUNNING && status != ITER_LIMIT) pst = status;   // lpo_ctx.status
 
-    // store the state
-    if (TIER == TIER_LDS && done > 0) {
-        for (int64_t i = i0; i < rows; i += ty)
-            for (int64_t j = j0; j < ncols; j += tx) gT[i * g.ld + j] = T[i * tp + j];
-    }
-    if (tid == 0) {
-        lp->status = status;
-        if (MODE != MODE_DUAL && status != RUNNING && status != ITER_LIMIT) lp->pstatus = status;
-        lp->pivots = pivots0 + done;
-        lp->last_k = last_k;
-        lp->last_r = last_r;
-        lp->budget = budget - done;
-        lp->objective = T[m * tp];
-        if (status == RUNNING) atomicAdd(g.running, 1);
-    }
+    v.store(work > 0);
+    if (v.tid == 0) batch_write_back(g, v, lp, status, pst, pivots, last_k, last_r, budget);
 }
 
 // ------------------------------------------------------------------------
@@ -396,85 +496,33 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
 // the transition between them in the workgroup that owns the LP
 // ------------------------------------------------------------------------
 
-// a two-phase call begins: every LP starts phase I again, whatever its status
-__global__ void k_batch_begin_two_phase(BatchLP *lp, int64_t count, int64_t budget) {
-    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= count) return;
-    lp[q].budget = budget;
-    lp[q].status = RUNNING;
-    lp[q].phase = PH_OBJ1;
-    lp[q].cursor = 0;
-}
-
 // Work of a launch: a pivot (drive-outs included) or an objective computation
 // is one unit, and a launch ends in front of the unit that would exceed
 // g.chunk. `budget` is the oracle's: phase I may apply max_pivots pivots,
 // phase II max(0, max_pivots - pivots of the LP); drive-outs are not charged.
 template <int RULE, int TIER>
 __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase t) {
-    extern __shared__ double smem[];
-    const int64_t b = blockIdx.x;
-    const int tid = threadIdx.x;
-    BatchLP *lp = g.lp + b;
+    BatchLP *lp = g.lp + blockIdx.x;
     if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
-    const int64_t m = g.m, rows = m + 1, ncols = g.ncols, af = t.art_first;
-    double *gT = g.T + b * rows * g.ld;
-    int64_t *gB = g.basis + b * m;
-    double *cost = t.cost + b * (ncols - 1);
-    // LDS as k_batch_solve: [tableau (TIER_LDS)] P[ncols] C[rows] [basis as int32 (TIER_LDS)]
-    const int64_t tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
-    double *T = TIER == TIER_LDS ? smem : gT;
-    double *sP = TIER == TIER_LDS ? smem + rows * tp : smem;
-    double *sC = sP + ncols;
-    int32_t *sB = (int32_t *)(sC + rows);
-    const int tx = 1 << g.txs, ty = kBlock >> g.txs;
-    const int j0 = tid & (tx - 1), i0 = tid >> g.txs;
-
+    const BatchView<TIER> v = BatchView<TIER>::make(g, g.m + 1);
+    const int64_t m = g.m, ncols = g.ncols, af = t.art_first, chunk = g.chunk;
+    double *cost = t.cost + (int64_t)blockIdx.x * (ncols - 1);
     int32_t phase = lp->phase, pst = lp->pstatus;
-    int64_t cursor = lp->cursor, pivots = lp->pivots, budget = lp->budget;
-    int64_t last_k = lp->last_k, last_r = lp->last_r;
-    const int64_t chunk = g.chunk;
-    if (TIER == TIER_LDS) {
-        for (int64_t i = i0; i < rows; i += ty)
-            for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * g.ld + j];
-        for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
-    }
-    __syncthreads();
+    int64_t cursor = lp->cursor, pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
+    v.load();
 
-    // (k, r) with pivot element piv: the update, the basis, the log, the counters
-    auto apply = [&](int64_t k, int64_t r, double piv) {
-        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, piv, tid, tx, ty, j0, i0);
-        if (tid == 0) {
-            gB[r] = k;
-            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
-            if (g.logk && pivots < g.logcap) {
-                g.logk[b * g.logcap + pivots] = (int32_t)k;
-                g.logr[b * g.logcap + pivots] = (int32_t)r;
-            }
-        }
-        last_k = k;
-        last_r = r;
-        pivots++;
-        __syncthreads();
-    };
-
+    int64_t nact = 0;
+    auto price = [&] { return batch_price<RULE>(v.T + m * v.tp, nact, g.eps_opt, v.tid); };
     int32_t status = RUNNING;                     // stays RUNNING where the launch ends in front of a unit
     int64_t work = 0;
     for (;;) {
         if (phase == PH_OBJ1 || phase == PH_OBJ2) {
             if (work >= chunk) break;
             if (phase == PH_OBJ1 && t.save_cost) {
-                for (int64_t j = 1 + tid; j < ncols; j += kBlock) cost[j - 1] = -T[m * tp + j];
+                for (int64_t j = 1 + v.tid; j < ncols; j += kBlock) cost[j - 1] = -v.T[m * v.tp + j];
             }
-            for (int64_t i = tid; i < m; i += kBlock) {
-                const int64_t bi = TIER == TIER_LDS ? (int64_t)sB[i] : gB[i];
-                // (a batch that was never given a basis holds zeros: no column, no cost)
-                sC[i] = phase == PH_OBJ1 ? (bi >= af ? -1.0 : 0.0) : (bi >= 1 ? cost[bi - 1] : 0.0);
-            }
-            __syncthreads();
-            if (phase == PH_OBJ1) batch_objective<true>(T, tp, m, ncols, sC, cost, af, tid);
-            else batch_objective<false>(T, tp, m, ncols, sC, cost, af, tid);
-            __syncthreads();
+            if (phase == PH_OBJ1) batch_objective<COST_ART>(v, m, cost, af);
+            else batch_objective<COST_REAL>(v, m, cost, af);
             pst = RUNNING;                        // lpo_set_objective
             if (phase == PH_OBJ2) budget = t.max_pivots > pivots ? t.max_pivots - pivots : 0;
             phase++;
@@ -483,29 +531,11 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
         }
         if (phase == PH_LOOP1 || phase == PH_LOOP2) {
             // lpo_solve over columns 1..N (phase I) or 1..art_first-1 (phase II)
-            const int64_t nact = phase == PH_LOOP1 ? ncols - 1 : af - 1;
-            int32_t st = RUNNING;
-            for (;;) {
-                const int64_t k = batch_price<RULE>(T + m * tp, nact, g.eps_opt, tid);   // also the final peek
-                if (k < 0) {
-                    st = OPTIMAL;
-                    break;
-                }
-                if (budget == 0) {
-                    st = ITER_LIMIT;
-                    break;
-                }
-                if (work >= chunk) break;
-                const Cand cb = batch_ratio<RULE, TIER>(T, tp, m, k, sB, gB, g.eps_piv, tid);
-                if (cb.row < 0) {
-                    st = UNBOUNDED;
-                    break;
-                }
-                if (!isfinite(cb.piv) || !isfinite(T[cb.row * tp])) {
-                    st = NUMERIC;
-                    break;
-                }
-                apply(k, cb.row, cb.piv);
+            nact = phase == PH_LOOP1 ? ncols - 1 : af - 1;
+            int32_t st;
+            while ((st = batch_primal_step<RULE>(v, price, g.eps_piv, budget, chunk - work, pivots, last_k, last_r)) ==
+                   STEP_APPLIED) {
+                pivots++;
                 budget--;
                 work++;
             }
@@ -519,10 +549,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
                 status = NUMERIC;
                 break;
             }
-            // feasibility: every thread adds the same column in row order
-            double bsum = 0;
-            for (int64_t i = 0; i < m; i++) bsum += fabs(T[i * tp]);
-            if (T[m * tp] < -1e-9 * (bsum > 1.0 ? bsum : 1.0)) {
+            if (v.artificials_positive()) {
                 status = INFEASIBLE;
                 break;
             }
@@ -534,10 +561,10 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
         // row, of either sign (b_i is zero there; no ratio test); a row without one keeps it
         bool full = false;
         for (; cursor < m; cursor++) {
-            if ((TIER == TIER_LDS ? (int64_t)sB[cursor] : gB[cursor]) < af) continue;
+            if (v.basis(cursor) < af) continue;
             PricePart pb{0.0, -1, 0, 0};
-            for (int64_t j = 1 + tid; j < af; j += kBlock) {
-                const double a = T[cursor * tp + j];
+            for (int64_t j = 1 + v.tid; j < af; j += kBlock) {
+                const double a = v.T[cursor * v.tp + j];
                 PricePart c{a, fabs(a) > g.eps_piv ? j : -1, 0, (int32_t)j};
                 pp_take(pb, c, pp_better<RULE_BLAND>(c, pb));
             }
@@ -547,29 +574,21 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
                 full = true;
                 break;
             }
-            apply(pb.j, cursor, pb.v);
+            v.apply(pb.j, cursor, pb.v, pivots);
+            last_k = pb.j;
+            last_r = cursor;
+            pivots++;
             work++;
         }
         if (full) break;
         phase = PH_OBJ2;
     }
 
-    // store the state
-    if (TIER == TIER_LDS && work > 0) {
-        for (int64_t i = i0; i < rows; i += ty)
-            for (int64_t j = j0; j < ncols; j += tx) gT[i * g.ld + j] = T[i * tp + j];
-    }
-    if (tid == 0) {
-        lp->status = status;
-        lp->pstatus = pst;
-        lp->pivots = pivots;
-        lp->last_k = last_k;
-        lp->last_r = last_r;
-        lp->budget = budget;
-        lp->objective = T[m * tp];
+    v.store(work > 0);
+    if (v.tid == 0) {
+        batch_write_back(g, v, lp, status, pst, pivots, last_k, last_r, budget);
         lp->phase = phase;
         lp->cursor = cursor;
-        if (status == RUNNING) atomicAdd(g.running, 1);
     }
 }
 
@@ -578,22 +597,6 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
 // the M part of the objective in row m, the real part in row m + 1
 // ------------------------------------------------------------------------
 
-// batch_objective for one of the two rows: MPART: row m from the costs -1 on
-// the artificial columns (art_first on) and 0 before; else row m + 1 from the
-// real costs, those of the artificial columns forced to 0. cB[i] holds c_B(i).
-template <bool MPART>
-__device__ __forceinline__ void batch_objective_big_m(double *T, int64_t tp, int64_t m, int64_t ncols, const double *cB,
-                                                      const double *cost, int64_t art_first, int tid) {
-    double *obj = T + (MPART ? m : m + 1) * tp;
-    for (int64_t j = tid; j < ncols; j += kBlock) {
-        double acc = 0.0;
-#pragma unroll 4
-        for (int64_t i = 0; i < m; i++) acc = fma(cB[i], T[i * tp + j], acc);
-        if (j > 0) acc = acc - (j >= art_first ? (MPART ? -1.0 : 0.0) : (MPART ? 0.0 : cost[j - 1]));
-        obj[j] = acc;
-    }
-}
-
 // Work of a launch as k_batch_two_phase's: a pivot or the computation of the
 // two objective rows is one unit. `t.cost` holds the real costs (written here
 // from row m + 1 when save_cost); lp->phase is PH_OBJ1 until the objective
@@ -601,121 +604,46 @@ __device__ __forceinline__ void batch_objective_big_m(double *T, int64_t tp, int
 // any unit is resumed bitwise by the next.
 template <int RULE, int TIER>
 __global__ __launch_bounds__(kBlock) void k_batch_big_m(BatchGeo g, TwoPhase t) {
-    extern __shared__ double smem[];
-    const int64_t b = blockIdx.x;
-    const int tid = threadIdx.x;
-    BatchLP *lp = g.lp + b;
+    BatchLP *lp = g.lp + blockIdx.x;
     if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
-    const int64_t m = g.m, rows = m + 2, ncols = g.ncols, af = t.art_first;
-    double *gT = g.T + b * rows * g.ld;
-    int64_t *gB = g.basis + b * m;
-    double *cost = t.cost + b * (ncols - 1);
-    // LDS: [tableau of m + 2 rows (TIER_LDS)] P[ncols] C[m + 2] [basis as int32 (TIER_LDS)]
-    const int64_t tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
-    double *T = TIER == TIER_LDS ? smem : gT;
-    double *sP = TIER == TIER_LDS ? smem + rows * tp : smem;
-    double *sC = sP + ncols;
-    int32_t *sB = (int32_t *)(sC + rows);
-    const int tx = 1 << g.txs, ty = kBlock >> g.txs;
-    const int j0 = tid & (tx - 1), i0 = tid >> g.txs;
-
+    const BatchView<TIER> v = BatchView<TIER>::make(g, g.m + 2);
+    const int64_t m = g.m, ncols = g.ncols, af = t.art_first, chunk = g.chunk;
+    double *cost = t.cost + (int64_t)blockIdx.x * (ncols - 1);
     int32_t phase = lp->phase, pst = lp->pstatus;
-    int64_t pivots = lp->pivots, budget = lp->budget;
-    int64_t last_k = lp->last_k, last_r = lp->last_r;
-    const int64_t chunk = g.chunk;
-    if (TIER == TIER_LDS) {
-        for (int64_t i = i0; i < rows; i += ty)
-            for (int64_t j = j0; j < ncols; j += tx) T[i * tp + j] = gT[i * g.ld + j];
-        for (int64_t i = tid; i < m; i += kBlock) sB[i] = (int32_t)gB[i];
-    }
-    __syncthreads();
+    int64_t pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
+    v.load();
 
-    int32_t status = RUNNING;                     // stays RUNNING where the launch ends in front of a unit
     int64_t work = 0;
     if (phase == PH_OBJ1) {
         // lpo_set_objective_m, lpo_set_objective: each row from the current basis (rows 0..m-1 only)
         if (t.save_cost) {
-            for (int64_t j = 1 + tid; j < ncols; j += kBlock) cost[j - 1] = -T[(m + 1) * tp + j];
+            for (int64_t j = 1 + v.tid; j < ncols; j += kBlock) cost[j - 1] = -v.T[(m + 1) * v.tp + j];
             __syncthreads();                      // the costs of the basic columns are read by other threads
         }
-        for (int64_t i = tid; i < m; i += kBlock)
-            sC[i] = (TIER == TIER_LDS ? (int64_t)sB[i] : gB[i]) >= af ? -1.0 : 0.0;
-        __syncthreads();
-        batch_objective_big_m<true>(T, tp, m, ncols, sC, cost, af, tid);
-        __syncthreads();
-        for (int64_t i = tid; i < m; i += kBlock) {
-            const int64_t bi = TIER == TIER_LDS ? (int64_t)sB[i] : gB[i];
-            // (a batch that was never given a basis holds zeros: no column, no cost)
-            sC[i] = (bi >= 1 && bi < af) ? cost[bi - 1] : 0.0;
-        }
-        __syncthreads();
-        batch_objective_big_m<false>(T, tp, m, ncols, sC, cost, af, tid);
-        __syncthreads();
+        batch_objective<COST_ART>(v, m, cost, af);
+        batch_objective<COST_REAL_NO_ART>(v, m + 1, cost, af);
         pst = RUNNING;                            // lpo_set_objective
         phase = PH_LOOP1;
         work = 1;
     }
     // lpo_solve over columns 1..N, priced on both rows
-    for (;;) {
-        const int64_t k = batch_price_big_m<RULE>(T + m * tp, T + (m + 1) * tp, ncols - 1, g.eps_opt, tid);   // also the final peek
-        if (k < 0) {
-            status = OPTIMAL;
-            break;
-        }
-        if (budget == 0) {
-            status = ITER_LIMIT;
-            break;
-        }
-        if (work >= chunk) break;
-        const Cand cb = batch_ratio<RULE, TIER>(T, tp, m, k, sB, gB, g.eps_piv, tid);
-        const int64_t r = cb.row;
-        if (r < 0) {
-            status = UNBOUNDED;
-            break;
-        }
-        if (!isfinite(cb.piv) || !isfinite(T[r * tp])) {
-            status = NUMERIC;
-            break;
-        }
-        batch_pivot(T, tp, rows, ncols, sP, sC, k, r, cb.piv, tid, tx, ty, j0, i0);
-        if (tid == 0) {
-            gB[r] = k;
-            if (TIER == TIER_LDS) sB[r] = (int32_t)k;
-            if (g.logk && pivots < g.logcap) {
-                g.logk[b * g.logcap + pivots] = (int32_t)k;
-                g.logr[b * g.logcap + pivots] = (int32_t)r;
-            }
-        }
-        last_k = k;
-        last_r = r;
+    auto price = [&] {
+        return batch_price_big_m<RULE>(v.T + m * v.tp, v.T + (m + 1) * v.tp, ncols - 1, g.eps_opt, v.tid);
+    };
+    int32_t status;                               // RUNNING where the launch ends in front of a unit
+    while ((status = batch_primal_step<RULE>(v, price, g.eps_piv, budget, chunk - work, pivots, last_k, last_r)) ==
+           STEP_APPLIED) {
         pivots++;
         budget--;
         work++;
-        __syncthreads();
     }
     if (status != RUNNING && status != ITER_LIMIT) pst = status;   // lpo_ctx.status
-    if (status == OPTIMAL || status == UNBOUNDED) {
-        // artificials still positive: every thread adds the same column in row order
-        double bsum = 0;
-        for (int64_t i = 0; i < m; i++) bsum += fabs(T[i * tp]);
-        if (T[m * tp] < -1e-9 * (bsum > 1.0 ? bsum : 1.0)) status = INFEASIBLE;
-    }
+    if ((status == OPTIMAL || status == UNBOUNDED) && v.artificials_positive()) status = INFEASIBLE;
 
-    // store the state
-    if (TIER == TIER_LDS && work > 0) {
-        for (int64_t i = i0; i < rows; i += ty)
-            for (int64_t j = j0; j < ncols; j += tx) gT[i * g.ld + j] = T[i * tp + j];
-    }
-    if (tid == 0) {
-        lp->status = status;
-        lp->pstatus = pst;
-        lp->pivots = pivots;
-        lp->last_k = last_k;
-        lp->last_r = last_r;
-        lp->budget = budget;
-        lp->objective = T[(m + 1) * tp];
+    v.store(work > 0);
+    if (v.tid == 0) {
+        batch_write_back(g, v, lp, status, pst, pivots, last_k, last_r, budget);
         lp->phase = phase;
-        if (status == RUNNING) atomicAdd(g.running, 1);
     }
 }
 
@@ -843,35 +771,13 @@ int alloc_log(lpg_batch *b, int64_t cap) {
     return 0;
 }
 
-template <int MODE, int TIER>
-int launch_solve_t(lpg_batch *b) {
-    static std::atomic<unsigned long long> attr{0};
-    const int dev = b->device & 63;
-    if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute((const void *)k_batch_solve<MODE, TIER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kBatchMaxLds) != hipSuccess) {
-            (void)hipGetLastError();
-            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(k_batch_solve, %d bytes of LDS) failed", kBatchMaxLds);
-        }
-        attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
-    }
-    hipLaunchKernelGGL((k_batch_solve<MODE, TIER>), dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream,
-                       bgeo(b));
-    return 0;
-}
+// which solver a call runs
+enum Method { M_PRIMAL, M_DUAL, M_TWO_PHASE, M_BIG_M };
 
-int launch_solve(lpg_batch *b, int mode) {
-    const bool l = b->tier == TIER_LDS;
-    switch (mode) {
-    case RULE_DANTZIG: return l ? launch_solve_t<RULE_DANTZIG, TIER_LDS>(b) : launch_solve_t<RULE_DANTZIG, TIER_GLOBAL>(b);
-    case RULE_BLAND: return l ? launch_solve_t<RULE_BLAND, TIER_LDS>(b) : launch_solve_t<RULE_BLAND, TIER_GLOBAL>(b);
-    default: return l ? launch_solve_t<MODE_DUAL, TIER_LDS>(b) : launch_solve_t<MODE_DUAL, TIER_GLOBAL>(b);
-    }
-}
-
-// one launch of K = k_batch_two_phase<RULE, TIER> or k_batch_big_m<RULE, TIER> (`name` for the error message)
-template <void (*K)(BatchGeo, TwoPhase)>
-int launch_art_t(lpg_batch *b, const TwoPhase &t, const char *name) {
+// one launch of solve kernel K (`name` for the error message), one workgroup
+// per LP; its dynamic LDS limit is raised once per device
+template <auto K, class... Args>
+int launch_lp(lpg_batch *b, const char *name, const Args &...args) {
     static std::atomic<unsigned long long> attr{0};
     const int dev = b->device & 63;
     if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
@@ -881,24 +787,29 @@ int launch_art_t(lpg_batch *b, const TwoPhase &t, const char *name) {
         }
         attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
     }
-    hipLaunchKernelGGL(K, dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream, bgeo(b), t);
+    hipLaunchKernelGGL(K, dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream, bgeo(b), args...);
     return 0;
 }
 
-int launch_two_phase(lpg_batch *b, int rule, const TwoPhase &t) {
-    const bool l = b->tier == TIER_LDS;
-    const char *n = "k_batch_two_phase";
-    if (rule == RULE_BLAND)
-        return l ? launch_art_t<k_batch_two_phase<RULE_BLAND, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_two_phase<RULE_BLAND, TIER_GLOBAL>>(b, t, n);
-    return l ? launch_art_t<k_batch_two_phase<RULE_DANTZIG, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_two_phase<RULE_DANTZIG, TIER_GLOBAL>>(b, t, n);
+template <int TIER>
+int launch_tier(lpg_batch *b, Method method, int rule, const TwoPhase &t) {
+    const bool bland = rule == RULE_BLAND;
+    switch (method) {
+    case M_DUAL: return launch_lp<k_batch_solve<MODE_DUAL, TIER>>(b, "k_batch_solve");
+    case M_PRIMAL:
+        return bland ? launch_lp<k_batch_solve<RULE_BLAND, TIER>>(b, "k_batch_solve")
+                     : launch_lp<k_batch_solve<RULE_DANTZIG, TIER>>(b, "k_batch_solve");
+    case M_TWO_PHASE:
+        return bland ? launch_lp<k_batch_two_phase<RULE_BLAND, TIER>>(b, "k_batch_two_phase", t)
+                     : launch_lp<k_batch_two_phase<RULE_DANTZIG, TIER>>(b, "k_batch_two_phase", t);
+    default:
+        return bland ? launch_lp<k_batch_big_m<RULE_BLAND, TIER>>(b, "k_batch_big_m", t)
+                     : launch_lp<k_batch_big_m<RULE_DANTZIG, TIER>>(b, "k_batch_big_m", t);
+    }
 }
 
-int launch_big_m(lpg_batch *b, int rule, const TwoPhase &t) {
-    const bool l = b->tier == TIER_LDS;
-    const char *n = "k_batch_big_m";
-    if (rule == RULE_BLAND)
-        return l ? launch_art_t<k_batch_big_m<RULE_BLAND, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_big_m<RULE_BLAND, TIER_GLOBAL>>(b, t, n);
-    return l ? launch_art_t<k_batch_big_m<RULE_DANTZIG, TIER_LDS>>(b, t, n) : launch_art_t<k_batch_big_m<RULE_DANTZIG, TIER_GLOBAL>>(b, t, n);
+int launch_solve(lpg_batch *b, Method method, int rule, const TwoPhase &t) {
+    return b->tier == TIER_LDS ? launch_tier<TIER_LDS>(b, method, rule, t) : launch_tier<TIER_GLOBAL>(b, method, rule, t);
 }
 
 // what a Big-M batch refuses (and a plain batch, for lpg_batch_solve_big_m)
@@ -925,12 +836,12 @@ int stage_costs(lpg_batch *b, const double *cost, int64_t ld_cost) {
     return 0;
 }
 
-// two == nullptr: k_batch_solve in `mode`; else k_batch_two_phase (k_batch_big_m on a Big-M batch) with rule `mode`
-int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const TwoPhase *two = nullptr) {
+// one solve call: `method` with `rule` (M_DUAL: RULE_DANTZIG); `t` for M_TWO_PHASE and M_BIG_M
+int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_result *out, const TwoPhase &t = {}) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "max_pivots < 0");
     BHIPCHK(b, hipSetDevice(b->device));
-    if (mode == MODE_DUAL) {
+    if (method == M_DUAL) {
         const unsigned long long none = ~0ull;
         unsigned long long bad = none;
         BHIPCHK(b, hipMemcpyAsync(b->bad, &none, sizeof none, hipMemcpyHostToDevice, b->stream));
@@ -942,25 +853,27 @@ int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const
             return bfail(b, LPG_ERR_STATE, "lpg_batch_solve_dual: LP %llu is not dual feasible (a d_j < -eps_opt); "
                                            "nothing has pivoted", bad);
     }
-    if (two)
+    // every launch spends `chunk` of each running LP's budget (or ends the LP)
+    int64_t max_launches = max_pivots / b->chunk + 2;
+    if (method == M_TWO_PHASE) {
+        // both phases have a budget of up to max_pivots, and the drive-out
+        // pivots (at most m) and the two objectives are work as well
+        max_launches = 2 * std::min<int64_t>(max_pivots / b->chunk, (int64_t)1 << 60) + (b->m + 2) / b->chunk + 4;
+    } else if (method == M_BIG_M) {
+        max_launches = max_pivots / b->chunk + 4;                 // the pivots and one objective unit
+    }
+    if (method == M_TWO_PHASE || method == M_BIG_M)
         hipLaunchKernelGGL(k_batch_begin_two_phase, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp,
                            b->count, max_pivots);
     else
         hipLaunchKernelGGL(k_batch_begin, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, b->count,
-                           max_pivots, mode == MODE_DUAL ? 1 : 0);
+                           max_pivots, method == M_DUAL ? 1 : 0);
     BHIPCHK(b, hipGetLastError());
     b->pivoted = true;
-    // every launch spends `chunk` of each running LP's budget (or ends the LP);
-    // two-phase: both phases have a budget of up to max_pivots, and the
-    // drive-out pivots (at most m) and the two objectives are work as well
-    int64_t max_launches = max_pivots / b->chunk + 2;
-    if (two) max_launches = 2 * std::min<int64_t>(max_pivots / b->chunk, (int64_t)1 << 60) + (b->m + 2) / b->chunk + 4;
-    if (two && b->nobj == 2) max_launches = max_pivots / b->chunk + 4;     // the pivots and one objective unit
     for (int64_t it = 0;; it++) {
         int32_t running = 0;
         BHIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
-        if (int rc = !two ? launch_solve(b, mode) : b->nobj == 2 ? launch_big_m(b, mode, *two) : launch_two_phase(b, mode, *two))
-            return rc;
+        if (int rc = launch_solve(b, method, rule, t)) return rc;
         BHIPCHK(b, hipGetLastError());
         BHIPCHK(b, hipMemcpyAsync(&running, b->running, sizeof running, hipMemcpyDeviceToHost, b->stream));
         BHIPCHK(b, hipStreamSynchronize(b->stream));
@@ -974,13 +887,49 @@ int batch_run(lpg_batch *b, int64_t max_pivots, int mode, lpg_result *out, const
         BHIPCHK(b, hipMemcpy(h.data(), b->lp, h.size() * sizeof(BatchLP), hipMemcpyDeviceToHost));
         for (int64_t q = 0; q < b->count; q++) {
             out[q].status = h[q].status;
-            out[q].rule = mode == RULE_BLAND ? LPG_RULE_BLAND : LPG_RULE_DANTZIG;
+            out[q].rule = rule == RULE_BLAND ? LPG_RULE_BLAND : LPG_RULE_DANTZIG;
             out[q].pivots = h[q].pivots;
             out[q].objective = h[q].objective;
             out[q].entering = h[q].last_k;
             out[q].leaving = h[q].last_r;
         }
     }
+    return 0;
+}
+
+// lpg_batch_solve_two_phase (M_TWO_PHASE) and lpg_batch_solve_big_m (M_BIG_M); `call` names the entry point
+int solve_artificial(lpg_batch *b, Method method, const char *call, int64_t art_first, const double *cost, int64_t ld_cost,
+                     int64_t max_pivots, int rule, lpg_result *out) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if ((b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
+    const int64_t N = b->ncols - 1;
+    if (art_first < 2 || art_first > N)
+        return bfail(b, LPG_ERR_ARG, "%s: art_first %lld outside 2..%lld", call, (long long)art_first, (long long)N);
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    if (cost && ld_cost < N)
+        return bfail(b, LPG_ERR_ARG, "%s: ld_cost %lld < N = %lld", call, (long long)ld_cost, (long long)N);
+    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
+    TwoPhase t{};
+    t.cost = b->cost;
+    t.art_first = art_first;
+    t.max_pivots = max_pivots;
+    t.save_cost = cost ? 0 : 1;
+    // two-phase: what phase II prices, and what a later lpg_batch_solve goes on with; Big-M prices all of 1..N
+    if (method == M_TWO_PHASE) b->nact = art_first - 1;
+    return batch_run(b, max_pivots, method, rule, out, t);
+}
+
+// lpg_batch_generate and lpg_batch_generate_artificial once the arguments are checked
+int generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
+    BHIPCHK(b, hipSetDevice(b->device));
+    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + b->nobj))), dim3(kBlock), 0, b->stream, bgeo(b),
+                       n, seed, kind);
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    b->pivoted = false;
     return 0;
 }
 
@@ -1160,14 +1109,7 @@ int lpg_batch_generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
                      (long long)(n + b->m + 1));
     if (kind != LPG_GEN_DENSE && kind != LPG_GEN_DEGENERATE && kind != LPG_GEN_DUAL)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: kind %d (dense, degenerate or dual only)", kind);
-    BHIPCHK(b, hipSetDevice(b->device));
-    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + 1))), dim3(kBlock), 0, b->stream, bgeo(b), n,
-                       seed, kind);
-    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    b->pivoted = false;
-    return 0;
+    return generate(b, n, seed, kind);
 }
 
 int lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt) {
@@ -1198,59 +1140,22 @@ int lpg_batch_reserve_log(lpg_batch *b, int64_t npivots) {
 int lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out) {
     if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_solve");
     if (b && rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve: rule %d", rule);
-    return batch_run(b, max_pivots, rule, out);
+    return batch_run(b, max_pivots, M_PRIMAL, rule, out);
 }
 
 int lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out) {
     if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_solve_dual");
-    return batch_run(b, max_pivots, MODE_DUAL, out);
+    return batch_run(b, max_pivots, M_DUAL, RULE_DANTZIG, out);
 }
 
 int lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
                               int rule, lpg_result *out) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
-    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_solve_two_phase");
-    const int64_t N = b->ncols - 1;
-    if (art_first < 2 || art_first > N)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: art_first %lld outside 2..%lld", (long long)art_first,
-                     (long long)N);
-    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: rule %d", rule);
-    if (cost && ld_cost < N)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: ld_cost %lld < N = %lld", (long long)ld_cost, (long long)N);
-    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_two_phase: max_pivots < 0");
-    BHIPCHK(b, hipSetDevice(b->device));
-    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
-    TwoPhase t{};
-    t.cost = b->cost;
-    t.art_first = art_first;
-    t.max_pivots = max_pivots;
-    t.save_cost = cost ? 0 : 1;
-    b->nact = art_first - 1;          // what phase II prices, and what a later lpg_batch_solve goes on with
-    return batch_run(b, max_pivots, rule, out, &t);
+    return solve_artificial(b, M_TWO_PHASE, "lpg_batch_solve_two_phase", art_first, cost, ld_cost, max_pivots, rule, out);
 }
 
 int lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
                           int rule, lpg_result *out) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
-    if (b->nobj != 2) return wrong_kind(b, "lpg_batch_solve_big_m");
-    const int64_t N = b->ncols - 1;
-    if (art_first < 2 || art_first > N)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: art_first %lld outside 2..%lld", (long long)art_first,
-                     (long long)N);
-    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: rule %d", rule);
-    if (cost && ld_cost < N)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: ld_cost %lld < N = %lld", (long long)ld_cost, (long long)N);
-    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve_big_m: max_pivots < 0");
-    BHIPCHK(b, hipSetDevice(b->device));
-    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
-    TwoPhase t{};
-    t.cost = b->cost;
-    t.art_first = art_first;
-    t.max_pivots = max_pivots;
-    t.save_cost = cost ? 0 : 1;
-    return batch_run(b, max_pivots, rule, out, &t);     // all columns 1..N are priced: nact stays N
+    return solve_artificial(b, M_BIG_M, "lpg_batch_solve_big_m", art_first, cost, ld_cost, max_pivots, rule, out);
 }
 
 int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
@@ -1272,13 +1177,7 @@ int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_
     if (n < 1 || b->ncols != n + b->m + 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate_artificial: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
                      (long long)(n + b->m + 1));
-    BHIPCHK(b, hipSetDevice(b->device));
-    hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + b->nobj))), dim3(kBlock), 0, b->stream, bgeo(b),
-                       n, seed, (int)LPG_GEN_ARTIFICIAL);
-    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    b->pivoted = false;
+    if (int rc = generate(b, n, seed, (int)LPG_GEN_ARTIFICIAL)) return rc;
     if (art_first) *art_first = 1 + n + (b->m + 1) / 2;
     return 0;
 }

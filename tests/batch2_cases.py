@@ -1,5 +1,5 @@
 """Two-phase batch test plumbing (tests/test_gpu_batch_two_phase.py,
-tests/batch2_worker.py), in the style of tests/batch_cases.py.
+tests/batch_worker.py), in the style of tests/batch_cases.py.
 
 A case is a JSON-able dict; run_batch(spec) runs it on the device through
 BatchEngine.solve_two_phase, run_oracle(spec) runs every LP of it through
@@ -108,40 +108,19 @@ def run_batch(s):
             assert af == art_first_of(s)
         else:
             e.load(*build_tableaus(s))
-        cost, calls = costs_of(s), []
-        for budget in s["budgets"]:
-            res = e.solve_two_phase(art_first_of(s), cost, budget, s["rule"])
-            calls.append([r.status for r in res])
-        info = e.info
-        out = bc._pack(res, e.get_rows(), e.get_basis(), [e.get_log(b) for b in range(B)], calls, info.log_capacity)
-        out["tier"] = np.array(info.tier, dtype=np.int64)
-        out["chunk"] = np.array(info.chunk, dtype=np.int64)
-        return out
+        cost = costs_of(s)
+        return bc.solve_and_read_back(e, s["budgets"], lambda budget: e.solve_two_phase(art_first_of(s), cost, budget,
+                                                                                        s["rule"]))
     finally:
         e.close()
 
 
 def run_oracle(s):
     """Every LP of the case through Oracle.solve_two_phase, one at a time."""
-    from oracle.lpo import Oracle
-    m, nc = s["m"], ncols_of(s)
+    nc, cost = ncols_of(s), costs_of(s)
     T, basis = build_tableaus(s)
-    cost = costs_of(s)
-    logcap = 2 * (m + nc)
-    results, rows, bas, logs, calls = [], [], [], [], [[] for _ in s["budgets"]]
-    for b in range(T.shape[0]):
-        o = Oracle(m, nc)
-        o.load_tableau(T[b], basis[b])
-        for c, budget in enumerate(s["budgets"]):
-            r = o.solve_two_phase(art_first_of(s), None if cost is None else cost[b, :nc - 1].copy(), budget, s["rule"])
-            calls[c].append(r.status)
-        results.append(r)
-        rows.append(o.get_rows())
-        bas.append(o.get_basis())
-        k, rr = o.get_log()
-        logs.append((k[:logcap], rr[:logcap]))
-        o.close()
-    return bc._pack(results, np.array(rows), np.array(bas), logs, calls, logcap)
+    return bc.oracle_loop(T, basis, s["budgets"], lambda o, b, budget: o.solve_two_phase(
+        art_first_of(s), None if cost is None else cost[b, :nc - 1].copy(), budget, s["rule"]), 2 * (s["m"] + nc))
 
 
 def phase_one(s):

@@ -1,5 +1,5 @@
 """Big-M batch test plumbing (tests/test_gpu_batch_big_m.py,
-tests/batch3_worker.py), in the style of tests/batch2_cases.py.
+tests/batch_worker.py), in the style of tests/batch2_cases.py.
 
 A case is a JSON-able dict; run_batch(spec) runs it on the device through a
 Big-M BatchEngine and solve_big_m, run_oracle(spec) runs every LP of it
@@ -115,41 +115,20 @@ def run_batch(s):
             assert af == art_first_of(s)
         else:
             e.load(*build_tableaus(s))
-        cost, calls = costs_of(s), []
-        for budget in s["budgets"]:
-            res = e.solve_big_m(art_first_of(s), cost, budget, s["rule"])
-            calls.append([r.status for r in res])
-        info = e.info
-        out = bc._pack(res, e.get_rows(), e.get_basis(), [e.get_log(b) for b in range(B)], calls, info.log_capacity)
-        out["tier"] = np.array(info.tier, dtype=np.int64)
-        out["chunk"] = np.array(info.chunk, dtype=np.int64)
-        out["nobj"] = np.array(info.nobj, dtype=np.int64)
-        return out
+        cost = costs_of(s)
+        return bc.solve_and_read_back(e, s["budgets"], lambda budget: e.solve_big_m(art_first_of(s), cost, budget, s["rule"]),
+                                      info_keys=("tier", "chunk", "nobj"))
     finally:
         e.close()
 
 
 def run_oracle(s, cost=None):
     """Every LP of the case through Oracle(nobj=2).solve_big_m, one at a time (cost: instead of costs_of(s))."""
-    from oracle.lpo import Oracle
-    m, nc = s["m"], ncols_of(s)
+    nc = ncols_of(s)
     T, basis = build_tableaus(s)
     cost = costs_of(s) if cost is None else cost
-    logcap = 2 * (m + nc)
-    results, rows, bas, logs, calls = [], [], [], [], [[] for _ in s["budgets"]]
-    for b in range(T.shape[0]):
-        o = Oracle(m, nc, nobj=2)
-        o.load_tableau(T[b], basis[b])
-        for c, budget in enumerate(s["budgets"]):
-            r = o.solve_big_m(art_first_of(s), None if cost is None else cost[b, :nc - 1].copy(), budget, s["rule"])
-            calls[c].append(r.status)
-        results.append(r)
-        rows.append(o.get_rows())
-        bas.append(o.get_basis())
-        k, rr = o.get_log()
-        logs.append((k[:logcap], rr[:logcap]))
-        o.close()
-    return bc._pack(results, np.array(rows), np.array(bas), logs, calls, logcap)
+    return bc.oracle_loop(T, basis, s["budgets"], lambda o, b, budget: o.solve_big_m(
+        art_first_of(s), None if cost is None else cost[b, :nc - 1].copy(), budget, s["rule"]), 2 * (s["m"] + nc), nobj=2)
 
 
 # the golden models whose rows lack a basic column, and how Big-M ends on them under both rules

@@ -16,6 +16,11 @@ only (solve LP `only` alone in a batch of 1).
 """
 from __future__ import annotations
 
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 
 SEED = 20220518
@@ -82,8 +87,56 @@ def _pack(results, rows, basis, logs, calls, logcap):
     }
 
 
+def in_subprocess(cases, specs, env, tmp_path):
+    """run_batch of module `cases` on every spec, on the device in a fresh process under `env` (tests/batch_worker.py)."""
+    sp, out = tmp_path / "specs.json", tmp_path / "out.npz"
+    sp.write_text(json.dumps(specs))
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "batch_worker.py")
+    p = subprocess.run([sys.executable, worker, cases, str(sp), str(out)], capture_output=True, text=True, timeout=300,
+                       env={**os.environ, **env})
+    assert p.returncode == 0, p.stderr[-2000:]
+    z = np.load(out)
+    return [{k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(f"{i}/")} for i in range(len(specs))]
+
+
+def solve_and_read_back(e, budgets, solve, info_keys=("tier", "chunk")):
+    """solve(budget) once per budget on BatchEngine e, then the read-back: _pack's dict plus info's `info_keys`."""
+    calls = []
+    for budget in budgets:
+        res = solve(budget)
+        calls.append([r.status for r in res])
+    info = e.info
+    out = _pack(res, e.get_rows(), e.get_basis(), [e.get_log(b) for b in range(len(res))], calls, info.log_capacity)
+    for key in info_keys:
+        out[key] = np.array(getattr(info, key), dtype=np.int64)
+    return out
+
+
+def oracle_loop(T, basis, budgets, solve, logcap, prepare=None, nobj=1):
+    """LP b of (T, basis) through an Oracle of its own: load, prepare(o), solve(o, b, budget) once per budget;
+    then _pack's dict, the log clipped to `logcap` (the batch records the first `capacity` pivots)."""
+    from oracle.lpo import Oracle
+    m, nc = T.shape[1] - nobj, T.shape[2]
+    results, rows, bas, logs, calls = [], [], [], [], [[] for _ in budgets]
+    for b in range(T.shape[0]):
+        o = Oracle(m, nc, nobj=nobj)
+        o.load_tableau(T[b], basis[b])
+        if prepare is not None:
+            prepare(o)
+        for c, budget in enumerate(budgets):
+            r = solve(o, b, budget)
+            calls[c].append(r.status)
+        results.append(r)
+        rows.append(o.get_rows())
+        bas.append(o.get_basis())
+        k, rr = o.get_log()
+        logs.append((k[:logcap], rr[:logcap]))
+        o.close()
+    return _pack(results, np.array(rows), np.array(bas), logs, calls, logcap)
+
+
 def run_batch(s):
-    """The case on the device; also returns info.tier / chunk / lds_bytes."""
+    """The case on the device; also returns info.tier / chunk."""
     import linearprogramming_amd as lpg
     B = 1 if s["only"] is not None else s["B"]
     e = lpg.BatchEngine(B, s["m"], ncols_of(s))
@@ -98,43 +151,24 @@ def run_batch(s):
             e.set_active_columns(s["nact"])
         if s["eps"] is not None:
             e.set_tolerances(*s["eps"])
-        calls = []
-        for budget in s["budgets"]:
-            res = e.solve_dual(budget) if s["dual"] else e.solve(budget, s["rule"])
-            calls.append([r.status for r in res])
-        info = e.info
-        out = _pack(res, e.get_rows(), e.get_basis(), [e.get_log(b) for b in range(B)], calls, info.log_capacity)
-        out["tier"] = np.array(info.tier, dtype=np.int64)
-        out["chunk"] = np.array(info.chunk, dtype=np.int64)
-        return out
+        return solve_and_read_back(e, s["budgets"], lambda budget: e.solve_dual(budget) if s["dual"] else
+                                   e.solve(budget, s["rule"]))
     finally:
         e.close()
 
 
 def run_oracle(s):
     """Every LP of the case through oracle.lpo.Oracle, one at a time."""
-    from oracle.lpo import Oracle
-    m, nc = s["m"], ncols_of(s)
-    T, basis = build_tableaus(s)
-    logcap = s["reserve_log"] if s["reserve_log"] is not None else 2 * (m + nc)
-    results, rows, bas, logs, calls = [], [], [], [], [[] for _ in s["budgets"]]
-    for b in range(T.shape[0]):
-        o = Oracle(m, nc)
-        o.load_tableau(T[b], basis[b])
+    def prepare(o):
         if s["nact"] is not None:
             o.set_active_columns(s["nact"])
         if s["eps"] is not None:
             o.set_tolerances(*s["eps"])
-        for c, budget in enumerate(s["budgets"]):
-            r = o.solve_dual(budget) if s["dual"] else o.solve(budget, s["rule"])
-            calls[c].append(r.status)
-        results.append(r)
-        rows.append(o.get_rows())
-        bas.append(o.get_basis())
-        k, rr = o.get_log()
-        logs.append((k[:logcap], rr[:logcap]))      # the batch records the first `capacity` pivots
-        o.close()
-    return _pack(results, np.array(rows), np.array(bas), logs, calls, logcap)
+
+    T, basis = build_tableaus(s)
+    logcap = s["reserve_log"] if s["reserve_log"] is not None else 2 * (s["m"] + ncols_of(s))
+    return oracle_loop(T, basis, s["budgets"], lambda o, b, budget: o.solve_dual(budget) if s["dual"] else
+                       o.solve(budget, s["rule"]), logcap, prepare)
 
 
 def bits(a):

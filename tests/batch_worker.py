@@ -1,12 +1,14 @@
-"""One batch case on the device in a process of its own: the batch reads
-LPG_BATCH_TIER / LPG_BATCH_CHUNK when it is created, so tests/test_gpu_batch.py
-runs the other tier and the small chunks here.
+"""Batch cases on the device in a process of their own: a batch reads
+LPG_BATCH_TIER / LPG_BATCH_CHUNK when it is created, so the tests/test_gpu_batch*.py
+run the other tier and the small chunks here.
 
-    python batch_worker.py SPECS.json OUT.npz
+    python batch_worker.py CASES SPECS.json OUT.npz
 
-SPECS.json: a list of batch_cases specs; OUT.npz: run_batch's arrays of case
-i under the prefix "i/".
+CASES: the module the specs belong to (batch_cases, batch2_cases or
+batch3_cases); SPECS.json: a list of its specs; OUT.npz: its run_batch's arrays
+of case i under the prefix "i/".
 """
+import importlib
 import json
 import os
 import sys
@@ -18,19 +20,18 @@ for p in (os.path.dirname(HERE), HERE):
 
 import numpy as np  # noqa: E402
 
-import batch_cases  # noqa: E402
 
-
-def main(specs_path, out_path):
+def main(cases_name, specs_path, out_path):
+    cases = importlib.import_module(cases_name)
     with open(specs_path) as f:
         specs = json.load(f)
     out = {}
     for i, s in enumerate(specs):
-        for key, val in batch_cases.run_batch(s).items():
+        for key, val in cases.run_batch(s).items():
             out[f"{i}/{key}"] = val
     np.savez(out_path, **out)
     return 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], sys.argv[3]))

@@ -10,7 +10,6 @@ from __future__ import annotations
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -25,7 +24,6 @@ pytestmark = pytest.mark.gpu
 OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT = 1, 2, 3, 4
 TIER_LDS, TIER_GLOBAL = 0, 1
 CLI = os.path.join(ROOT, "host", "lpgcli")
-WORKER = os.path.join(ROOT, "tests", "batch_worker.py")
 
 LDS_SHAPES = [(2, 2), (5, 6), (37, 70), (20, 300), (120, 3), (64, 128)]
 GLOBAL_SHAPES = [(96, 160), (130, 60), (300, 10)]
@@ -51,13 +49,7 @@ def check(s, tier=None):
 
 def in_subprocess(specs, env, tmp_path):
     """The cases on the device in a fresh process under `env` (tests/batch_worker.py)."""
-    sp, out = tmp_path / "specs.json", tmp_path / "out.npz"
-    sp.write_text(json.dumps(specs))
-    p = subprocess.run([sys.executable, WORKER, str(sp), str(out)], capture_output=True, text=True, timeout=300,
-                       env={**os.environ, **env})
-    assert p.returncode == 0, p.stderr[-2000:]
-    z = np.load(out)
-    return [{k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(f"{i}/")} for i in range(len(specs))]
+    return bc.in_subprocess("batch_cases", specs, env, tmp_path)
 
 
 # ---- shapes per tier -------------------------------------------------------
@@ -171,6 +163,18 @@ def test_two_calls_equal_one():
 def test_small_chunks_equal_the_default(chunk, tmp_path):
     for s, got in zip(CONTINUATION, in_subprocess(CONTINUATION, {"LPG_BATCH_CHUNK": str(chunk)}, tmp_path)):
         assert int(got["chunk"]) == chunk
+        bc.assert_same(got, oracle_of(s))
+
+
+GLOBAL_CHUNKED = [spec(5, 6), spec(12, 20, kind=GEN_DUAL, dual=True),
+                  spec(16, 16, kind=GEN_DEGENERATE, rule=RULE_BLAND, reserve_log=50 * 32)]
+
+
+def test_global_tier_under_small_chunks(tmp_path):
+    """Plain, dual and Bland on the global tier, resumed every 3 pivots."""
+    env = {"LPG_BATCH_TIER": "global", "LPG_BATCH_CHUNK": "3"}
+    for s, got in zip(GLOBAL_CHUNKED, in_subprocess(GLOBAL_CHUNKED, env, tmp_path)):
+        assert int(got["tier"]) == TIER_GLOBAL and int(got["chunk"]) == 3
         bc.assert_same(got, oracle_of(s))
 
 

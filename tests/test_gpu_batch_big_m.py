@@ -14,7 +14,6 @@ from __future__ import annotations
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -29,7 +28,6 @@ pytestmark = pytest.mark.gpu
 
 TIER_LDS, TIER_GLOBAL = 0, 1
 CLI = os.path.join(ROOT, "host", "lpgcli")
-WORKER = os.path.join(ROOT, "tests", "batch3_worker.py")
 LP_DIRS = [os.path.join(ROOT, "tests", "golden", d) for d in ("lp", "lp_extra")]
 
 # (95, 95) is the last square shape whose m + 2 rows fit the LDS cap (150,904 of 153,600 bytes);
@@ -67,14 +65,8 @@ def check(s, tier=None):
 
 
 def in_subprocess(specs, env, tmp_path):
-    """The cases on the device in a fresh process under `env` (tests/batch3_worker.py)."""
-    sp, out = tmp_path / "specs.json", tmp_path / "out.npz"
-    sp.write_text(json.dumps(specs))
-    p = subprocess.run([sys.executable, WORKER, str(sp), str(out)], capture_output=True, text=True, timeout=300,
-                       env={**os.environ, **env})
-    assert p.returncode == 0, p.stderr[-2000:]
-    z = np.load(out)
-    return [{k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(f"{i}/")} for i in range(len(specs))]
+    """The cases on the device in a fresh process under `env` (tests/batch_worker.py)."""
+    return bc.in_subprocess("batch3_cases", specs, env, tmp_path)
 
 
 def _shape_property(m, n, want):

@@ -1094,6 +1094,18 @@ int lpg_create_dist(lpg_ctx **out, int device, int world, int rank, int64_t m, i
         delete c;
         return LPG_ERR_ARG;
     }
+    // the block pass addresses a band of the tableau with 32-bit offsets
+    // (flushw_fits): wider tableaus update eagerly by default and refuse LPG_DEFER
+    const bool fits = !c->defer_k || flushw_fits(c->ld, ncols, std::max<int64_t>((c->nloc + 63) & ~(int64_t)63, 64),
+                                                 flush_kmax_supported(c->defer_k));
+    if (!fits && !dk) c->defer_k = 0;
+    if (!fits && dk) {
+        fail(c, LPG_ERR_ARG, "deferred updates (LPG_DEFER=%d) need 16 rows of the tableau below 2 GB: %lld columns are "
+             "too many (LPG_DEFER=0 updates eagerly)", c->defer_k, (long long)ncols);
+        snprintf(g_err, sizeof g_err, "%s", c->err);
+        delete c;
+        return LPG_ERR_ARG;
+    }
 #ifdef LPG_TEST_HOOKS
     // the test-hook build only (linearprogramming_amd/liblpg_testhooks.so,
     // Makefile): the product library never reads this variable

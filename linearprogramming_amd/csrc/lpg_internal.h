@@ -284,6 +284,15 @@ __host__ __device__ inline void flush_item(int64_t item, int64_t ntiles, int64_t
     }
     if (i1 > nloc) i1 = nloc;
 }
+// k_flushw (lpg_flushw.h) addresses a 16-row band of the tableau and the
+// live slots of Cbuf as buffers with 32-bit byte offsets, bit 31 marking a
+// lane that must stay out of memory: 15 rows and a row's columns, and kmax
+// slots of cs multipliers, must fit 31 bits. Config 4 (ld = 196,672) fits.
+__host__ __device__ inline bool flushw_fits(int64_t ld, int64_t ncols, int64_t cs, int kmax) {
+    const int64_t lim = (int64_t)1 << 31;
+    return ld > 0 && ncols <= ld && 16 * ld * 8 < lim && 15 * ld * 8 + 8 * ncols < lim && cs > 0 && kmax > 0 &&
+           cs < lim / 8 / kmax;
+}
 // XCD-grouped item map of k_flushw: the persistent blocks b with the same
 // b % 8 share one XCD (one L2), and group g = b % 8 dequeues from its own
 // queue (DevState::gwork[g]) the items of one row band x column class: band

@@ -20,6 +20,7 @@
 
 #include "lpg_internal.h"
 #include "lpg_device.h"
+#include "lpg_flushw.h"
 
 namespace lpg {
 
@@ -1705,8 +1706,6 @@ int launch_update(const Launch &L, const Geo &g, DevState *st, int s, const doub
 // step's tableau loads are issued before the current step's MFMAs.
 // ------------------------------------------------------------------------
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 template <int KMAX, int NPAIR, bool NT, int SR, int LB>
 __global__ __launch_bounds__(kBlock, LB > 0 ? LB : 1) void k_flushm(double *__restrict__ T, Geo g, DevState *__restrict__ st,
                                                    const double *__restrict__ Pbuf, const double *__restrict__ Cbuf,
@@ -1837,207 +1836,7 @@ __global__ __launch_bounds__(kBlock, LB > 0 ? LB : 1) void k_flushm(double *__re
     if (threadIdx.x == 0 && touched) atomicAdd(&st->touched, touched);
 }
 
-// k_flushw: k_flushm's wave tile (16 rows x 32 columns, 16-byte accesses,
-// even/odd-column MFMA chains, B fragments in VGPRs) on TALL items, which is
-// what keeps 64-pivot blocks memory-bound. A block's 4 waves sweep `rows`
-// rows (runtime, multiple of 16) of a 128-column tile in 16-row bands, in
-// step: the multipliers of band s (-C_q[i] in A-fragment order [q][row],
-// 8 KB at KMAX = 64) sit in an NB-deep LDS ring, loaded into registers one
-// band ahead and written one barrier later, and tableau band s+1 is loaded
-// while band s is on the matrix cores. k_flushm instead stages the C of a
-// whole 64-128-row strip per item (the LDS tile caps the strip at 64 rows
-// for 64 slots) and restarts its pipeline per item: 2.36 ms vs 1.64 ms for
-// this kernel at config 3, K = 64 (tools/flush_lab.hip,
-// profiles/r01_flush_lab_k64.log). Same chain, same MFMA, bitwise identical.
-// WPB waves per block: a tile is 32 * WPB columns wide, and every column
-// tile reads all of C once (WPB = 8 halves that on-chip traffic: C is
-// 8.4 MB at config 3, read by every tile from the Infinity Cache).
-template <int KMAX, int NB, int LB, int WPB = 4>
-__global__ __launch_bounds__(64 * WPB, LB) void k_flushw(double *__restrict__ T, Geo g, DevState *__restrict__ st,
-                                                         const double *__restrict__ Pbuf,
-                                                         const double *__restrict__ Cbuf, int64_t cs, int64_t ntiles,
-                                                         int64_t nitems, int64_t rows, int skip, FlushX X,
-                                                         const int32_t *__restrict__ tlive,
-                                                         const int64_t *__restrict__ lv,
-                                                         const int32_t *__restrict__ inv) {
-    constexpr int NTH = 64 * WPB;
-    constexpr int G = KMAX / 4;
-    constexpr int BAND = KMAX * 16;                 // doubles per band
-    constexpr int NPC = BAND / 2;                   // 16-byte multiplier pieces per band
-    constexpr int PER = (NPC + NTH - 1) / NTH;      // ... per thread (the last round partial when NTH does not divide)
-    static_assert(PER >= 1, "band staging");
-    __shared__ __attribute__((aligned(16))) double sC[NB][BAND];
-    __shared__ int64_t next_item;
-    __shared__ int next_grp;
-    __shared__ int wsum[WPB];
-    const int np = (int)st->npend;
-    if (np <= 0) return;
-    const int64_t ld = g.ld;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lc = lane & 15, lk = lane >> 4;
-    unsigned long long touched = 0;
-    const int g0 = (int)(blockIdx.x & 7);   // blocks with the same b % 8 share an XCD
-    int gd = 0;                             // X.on: queue g0 + gd (mod 8) is being drained
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (X.on) {
-                int64_t it = -1;
-                int grp = 0;
-                for (; gd < 8; gd++) {
-                    grp = (g0 + gd) & 7;
-                    const int64_t cnt = flushx_group(X, grp).count;
-                    if (cnt == 0) continue;
-                    it = (int64_t)atomicAdd(&st->gwork[grp], 1ull);
-                    if (it < cnt) break;
-                    it = -1;
-                }
-                next_item = it;
-                next_grp = grp;
-            } else {
-                next_item = (int64_t)atomicAdd(&st->fwork, 1ull);
-            }
-        }
-        __syncthreads();
-        const int64_t item = next_item;
-        int64_t tile, i0, i1;
-        if (X.on) {
-            if (item < 0) break;
-            const int grp = next_grp;
-            flushx_item(X, flushx_group(X, grp), grp, item, tile, i0, i1);
-        } else {
-            if (item >= nitems) break;
-            flush_item(item, ntiles, rows, g.nloc, tile, i0, i1);
-        }
-        // region mode (launch_flush_main): a tile without block-start nonbasic
-        // columns holds live entries only in a leaving column of the block, if
-        // any (one whose trade did not move it); otherwise it is skipped
-        // without reading its pending P entries
-        if (tlive) {
-            constexpr int NCH = 32 * WPB / 64;
-            const int64_t ch = tile * NCH + threadIdx.x;
-            const bool maybe = threadIdx.x < NCH && ch < ld / 64 && tlive[ch] != 0;
-            if (!__syncthreads_or(maybe)) {
-                bool hit = false;
-                if ((int)threadIdx.x < np) {
-                    const int64_t L = lv[threadIdx.x];
-                    if (L > 0) {
-                        const int64_t p = inv[L];
-                        hit = p >= tile * (32 * WPB) && p < (tile + 1) * (32 * WPB);
-                    }
-                }
-                if (!__syncthreads_or(hit)) continue;
-            }
-        }
-        const int64_t cl = tile * (32 * WPB) + wave * 32 + 2 * lc;   // this lane's column pair
-        const bool in = cl < g.ncols;                                // cl even, ld even: cl + 1 < ld
-        double be[G], bo[G];
-        bool live = false;
-#pragma unroll
-        for (int gq = 0; gq < G; gq++) {
-            const int q = 4 * gq + lk;
-            d2 v = d2{0.0, 0.0};
-            if (in && q < np) v = *(const d2 *)(Pbuf + (int64_t)q * ld + cl);
-            be[gq] = v.x;
-            bo[gq] = v.y;
-            live = live || v.x != 0.0 || v.y != 0.0;
-        }
-        // a column pair is live if any of its P entries over all slots is
-        // non-zero: OR over the 4 lanes holding its k-slices
-        live = (__shfl_xor((int)live, 16, 64) | (int)live) != 0;
-        live = (__shfl_xor((int)live, 32, 64) | (int)live) != 0;
-        const bool ok = in && (!skip || live);
-        int mine = (lk == 0 && ok) ? (cl + 1 < g.ncols ? 2 : 1) : 0;   // live doubles per row, pairs counted once
-        for (int mask = 32; mask > 0; mask >>= 1) mine += __shfl_xor(mine, mask, 64);
-        const bool wlive = mine > 0;                                   // wave-uniform
-        if (lane == 0) wsum[wave] = mine;
-        if (__syncthreads_count(wlive && lane == 0) == 0) continue;    // the whole tile is skipped
-        if (threadIdx.x == 0) {
-            int sum = 0;
-#pragma unroll
-            for (int w = 0; w < WPB; w++) sum += wsum[w];
-            touched += (unsigned long long)sum * (unsigned long long)(i1 - i0);
-        }
-        const int nb = (int)((i1 - i0 + 15) / 16);
-        // multiplier piece e of band s: slot q = e / 8, band rows 2 (e % 8) .. +1
-        // (zeros past np and past i1: A = -0 there, x + -0 == x)
-        auto cload = [&](d2 (&cr)[PER], int s) {
-#pragma unroll
-            for (int u = 0; u < PER; u++) {
-                const int e = threadIdx.x + u * NTH;
-                const int q = e >> 3, rr = 2 * (e & 7);
-                const int64_t row = i0 + 16 * s + rr;
-                d2 v = d2{0.0, 0.0};
-                if (s < nb && q < np && row < i1 && (NPC % NTH == 0 || e < NPC))
-                    v = *(const d2 *)(Cbuf + (int64_t)q * cs + row);   // row + 1 < cs
-                cr[u] = -v;
-            }
-        };
-        auto cstore = [&](const d2 (&cr)[PER], int s) {
-#pragma unroll
-            for (int u = 0; u < PER; u++)
-                if (NPC % NTH == 0 || threadIdx.x + u * NTH < NPC) *(d2 *)(&sC[s % NB][2 * (threadIdx.x + u * NTH)]) = cr[u];
-        };
-        for (int s = 0; s < NB - 1; s++) {   // prologue: bands 0 .. NB-2 into the ring
-            d2 cr[PER];
-            cload(cr, s);
-            cstore(cr, s);
-        }
-        d2 cn[PER];
-        cload(cn, NB - 1);
-        auto tload = [&](d2 (&x)[4], int s) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int64_t row = i0 + 16 * s + lk + 4 * r;
-                x[r] = (ok && row < i1) ? __builtin_nontemporal_load((const d2 *)(T + row * ld + cl)) : d2{0.0, 0.0};
-            }
-        };
-        d2 t[4];
-        tload(t, 0);
-        for (int s = 0; s < nb; s++) {
-            d2 tn[4];                         // one band ahead (two ahead measured no faster)
-            if (s + 1 < nb) tload(tn, s + 1);
-            __syncthreads();                  // band s is staged; ring slot (s - 1) % NB is free
-            cstore(cn, s + NB - 1);
-            cload(cn, s + NB);
-            if (wlive) {
-                d4 ae = d4{t[0].x, t[1].x, t[2].x, t[3].x};
-                d4 ao = d4{t[0].y, t[1].y, t[2].y, t[3].y};
-                const double *sa = &sC[s % NB][lk * 16 + lc];
-                // the next pair of A operands is read while this pair's four
-                // MFMAs run: left to the scheduler, every ds_read sat behind
-                // the MFMAs of the pair before and the chain waited an LDS
-                // round trip per four MFMAs (config 3, K = 96: 29.7-29.8k vs
-                // 28.6-28.8k pivots/s, profiles/r05_ab_flushw_aprefetch.log)
-                double a0 = sa[0], a1 = sa[64];
-#pragma unroll
-                for (int gq = 0; gq < G; gq += 2) {
-                    double n0 = 0.0, n1 = 0.0;
-                    if (gq + 2 < G) {
-                        n0 = sa[(gq + 2) * 64];
-                        n1 = sa[(gq + 3) * 64];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);   // the reads stay in front of the MFMAs
-                    ae = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, be[gq], ae, 0, 0, 0);
-                    ao = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bo[gq], ao, 0, 0, 0);
-                    ae = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, be[gq + 1], ae, 0, 0, 0);
-                    ao = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bo[gq + 1], ao, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    a0 = n0;
-                    a1 = n1;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = i0 + 16 * s + lk + 4 * r;
-                    if (ok && row < i1) __builtin_nontemporal_store(d2{ae[r], ao[r]}, (d2 *)(T + row * ld + cl));
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) t[r] = tn[r];
-        }
-    }
-    if (threadIdx.x == 0 && touched) atomicAdd(&st->touched, touched);
-}
+// k_flushw, the banded block pass (64-pivot blocks and above by default): lpg_flushw.h
 
 // The pivot rows of the block, after the block pass: row r_q (q its last
 // pivot in the block) = P_q continued by the chain of the later pivots,
@@ -2636,6 +2435,7 @@ int launch_flush_main(const Launch &L, const Geo &g, DevState *st, const Defer &
     hipStream_t stream = (hipStream_t)L.stream;
     if (kmax >= 64) which = 1;                              // k_flushm's C tile caps it at 32 slots
     if (which == 1) {
+        if (!flushw_fits(g.ld, g.ncols, D.cs, kmax)) return -1;   // lpg_create refuses such a context
         // k_flushw: 4-wave blocks, 128-column x 2048-row items swept in 16-row
         // bands with a 2-deep LDS ring of multipliers; small tableaus shrink
         // the items until they fill the chip

@@ -307,7 +307,7 @@ int  lpg_set_timing(lpg_ctx *ctx, int enable);
 int  lpg_get_timing(lpg_ctx *ctx, lpg_timing *out);          /* syncs; resets the sums */
 int  lpg_device_sync(lpg_ctx *ctx);
 
-/* ---- batches: many small LPs of one shape in one launch ----
+/* ---- batches: many small LPs in one launch ----
  * An lpg_ctx spreads ONE tableau over the chip; a caller with a thousand
  * small LPs (parameter sweeps, scenario sets, the node LPs of a
  * branch-and-bound tree, SURVEY.md:72) would loop create / solve / destroy.
@@ -351,8 +351,25 @@ int  lpg_device_sync(lpg_ctx *ctx);
  * calls refuse a Big-M batch and lpg_batch_solve_big_m a plain one
  * (LPG_ERR_STATE, nothing has pivoted).
  *
- * Not supported: mixed shapes (pad with zero rows or columns, which never
- * pivot); LPG_FLAG_NO_LOG is the only flag.
+ * Ragged batches: a batch from lpg_batch_create_ragged holds LPs of
+ * different shapes, LP q being (m_q + nobj) x ncols_q (nobj 1, or 2 for a
+ * Big-M batch; one kind per batch). Every solve call runs on it as on a batch
+ * of one shape -- one workgroup per LP, the same kernels, every LP bit for bit
+ * what it computes alone -- with the geometry, the tier (lpg_batch_shape) and
+ * the LDS layout decided per LP. A round of a solve call is one launch per
+ * tier in use: the global-tier LPs (group 0), then the LDS-tier LPs (group
+ * 1) with the dynamic LDS of the largest of them, in each the LPs with the
+ * most update work first. `chunk` and the log capacity,
+ * 2 * (max m + max ncols) by default, hold for the whole batch. Tableaus,
+ * bases and costs move in the packed layout: LP after LP, each dense with no
+ * padding (lpg_batch_load_packed and the other _packed / _ragged calls); the
+ * calls that take one shape or one pitch (lpg_batch_load, _get_rows,
+ * _get_basis, _set_objective, _set_active_columns, the generators, the scalar
+ * _solve_two_phase and _solve_big_m) return LPG_ERR_STATE on a ragged batch
+ * and name the call to use, and the packed calls refuse a batch of one shape
+ * in the same way; nothing is moved and nothing pivots.
+ *
+ * LPG_FLAG_NO_LOG is the only flag.
  * Every argument is validated on the host before any launch. One batch per
  * host thread; not reentrant. */
 #define LPG_BATCH_TIER_LDS    0
@@ -368,8 +385,22 @@ typedef struct {
     int64_t lds_bytes;            /* dynamic LDS of one workgroup */
     int64_t log_capacity;         /* pivots recorded per LP (0 with LPG_FLAG_NO_LOG) */
     int32_t nobj;                 /* objective rows per tableau: 1, or 2 for a Big-M batch */
+    /* ragged: 1 for a batch from lpg_batch_create_ragged (m, ncols, ld and
+     * lds_bytes above are then the largest of any LP, tier is
+     * LPG_BATCH_TIER_GLOBAL if any LP is on it), else 0 */
     int32_t pad;
 } lpg_batch_info_t;
+
+/* One LP of a ragged batch (lpg_batch_shape) */
+typedef struct {
+    int64_t m, ncols, ld;         /* constraint rows, N+1 columns, device row pitch (doubles) */
+    int32_t tier;                 /* LPG_BATCH_TIER_* of this LP */
+    int32_t group;                /* its launch group: 0 on the global tier, 1 on the LDS tier */
+    int64_t lds_bytes;            /* dynamic LDS its workgroup uses */
+    int64_t tableau_offset;       /* of its (m + nobj) x ncols tableau in the packed tableaus of the whole batch (doubles) */
+    int64_t basis_offset;         /* of its m entries in the packed bases */
+    int64_t cost_offset;          /* of its ncols - 1 entries in the packed costs */
+} lpg_batch_shape_t;
 
 /* count >= 1 LPs of m constraint rows and ncols = N+1 columns; flags: 0 or
  * LPG_FLAG_NO_LOG (anything else: LPG_ERR_ARG). All tableaus start as zeros
@@ -382,6 +413,32 @@ int  lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int
  * lpg_batch_generate_artificial puts the objective into row m + 1 (the M row
  * is zero). */
 int  lpg_batch_create_big_m(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags);
+/* A ragged batch: LP q has m[q] constraint rows and ncols[q] columns; nobj =
+ * 1 (a plain batch) or 2 (a Big-M batch) for all of them. LPG_ERR_ARG, with
+ * a message that names the first offending LP, before any device work: NULL
+ * arrays, count < 1, an LP with m < 1, ncols < 2 or m + nobj or ncols over
+ * LPG_BATCH_MAX_DIM, flags other than LPG_FLAG_NO_LOG, another nobj, more
+ * than 2^31 - 1 rows in all. */
+int  lpg_batch_create_ragged(lpg_batch **out, int device, int64_t count, const int64_t *m, const int64_t *ncols,
+                             int nobj, uint32_t flags);
+/* LP lp of a ragged batch (a batch of one shape: LPG_ERR_STATE, see lpg_batch_info) */
+int  lpg_batch_shape(const lpg_batch *b, int64_t lp, lpg_batch_shape_t *out);
+/* lpg_batch_load / _get_rows / _get_basis / _set_objective for a ragged
+ * batch, in the packed layout: LP q's tableau is (m_q + nobj) x ncols_q,
+ * row-major without padding, the LPs one after another from `first`; bases
+ * m_q entries each (validated: 1..N_q; NULL keeps them); costs ncols_q - 1
+ * entries each, for the whole batch. */
+int  lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, const int64_t *basis);
+int  lpg_batch_get_rows_packed(lpg_batch *b, int64_t first, int64_t n, double *out);
+int  lpg_batch_get_basis_packed(lpg_batch *b, int64_t first, int64_t n, int64_t *basis);
+int  lpg_batch_set_objective_packed(lpg_batch *b, const double *cost);
+/* lpg_batch_solve_two_phase / lpg_batch_solve_big_m on a ragged batch:
+ * art_first[q] in 2..N_q for LP q, cost packed or NULL (as the scalar calls').
+ * After the two-phase call LP q's active columns are 1..art_first[q]-1. */
+int  lpg_batch_solve_two_phase_ragged(lpg_batch *b, const int64_t *art_first, const double *cost,
+                                      int64_t max_pivots, int rule, lpg_result *out);
+int  lpg_batch_solve_big_m_ragged(lpg_batch *b, const int64_t *art_first, const double *cost,
+                                  int64_t max_pivots, int rule, lpg_result *out);
 void lpg_batch_destroy(lpg_batch *b);                        /* NULL is a no-op */
 const char *lpg_batch_last_error(const lpg_batch *b);        /* NULL: this thread's last create error */
 int  lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *out);

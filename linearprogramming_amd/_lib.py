@@ -60,6 +60,13 @@ class BatchInfo(ctypes.Structure):
                 ("log_capacity", ctypes.c_int64), ("nobj", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class BatchShape(ctypes.Structure):
+    """lpg_batch_shape_t."""
+    _fields_ = [("m", ctypes.c_int64), ("ncols", ctypes.c_int64), ("ld", ctypes.c_int64),
+                ("tier", ctypes.c_int32), ("group", ctypes.c_int32), ("lds_bytes", ctypes.c_int64),
+                ("tableau_offset", ctypes.c_int64), ("basis_offset", ctypes.c_int64), ("cost_offset", ctypes.c_int64)]
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, c_double_p, ctypes.c_size_t)
 
@@ -134,6 +141,17 @@ PROTOTYPES = [
     ("lpg_batch_get_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64]),
     ("lpg_batch_get_basis", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p]),
     ("lpg_batch_get_log", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p, ctypes.c_int64]),
+    ("lpg_batch_create_ragged", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, c_int64_p,
+                                               c_int64_p, ctypes.c_int, ctypes.c_uint32]),
+    ("lpg_batch_shape", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(BatchShape)]),
+    ("lpg_batch_load_packed", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, c_int64_p]),
+    ("lpg_batch_get_rows_packed", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p]),
+    ("lpg_batch_get_basis_packed", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p]),
+    ("lpg_batch_set_objective_packed", ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    ("lpg_batch_solve_two_phase_ragged", ctypes.c_int, [ctypes.c_void_p, c_int64_p, c_double_p, ctypes.c_int64,
+                                                        ctypes.c_int, ctypes.POINTER(Result)]),
+    ("lpg_batch_solve_big_m_ragged", ctypes.c_int, [ctypes.c_void_p, c_int64_p, c_double_p, ctypes.c_int64,
+                                                    ctypes.c_int, ctypes.POINTER(Result)]),
 ]
 
 

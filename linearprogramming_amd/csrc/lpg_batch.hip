@@ -1,5 +1,5 @@
-// lpg_batch.hip — many small LPs of one shape in one launch: one workgroup
-// per LP (include/lpg.h, "batches").
+// lpg_batch.hip — many small LPs in one launch: one workgroup per LP
+// (include/lpg.h, "batches"); of one shape, or each of its own (a ragged batch).
 //
 // The context of lpg_ctx.hip spreads one tableau over the chip and pays a
 // launch-sized cost per pivot whatever the tableau size. Here the chip is
@@ -32,6 +32,14 @@
 // are their method's state machine over one set of parts: BatchView (where
 // the LP lives, load / store, apply a pivot), batch_primal_step (one step of
 // lpo_solve), batch_objective (an objective row) and batch_write_back.
+//
+// Ragged batches (lpg_batch_create_ragged): every LP has its own m and ncols,
+// kept in a BatchShape record in device memory. A workgroup reads which LP it
+// owns (BatchGeo::order) and that LP's record once at kernel entry (lp_geo;
+// both addresses depend on blockIdx.x alone, so the fields are scalar) and from
+// there on runs the code of a uniform batch. RG, the last template parameter
+// of the solve kernels, says which of the two a launch is: a uniform batch
+// runs the instantiations it ran before there were ragged ones.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -86,9 +94,21 @@ struct TwoPhase {
     int32_t save_cost;        // cost == NULL: the costs are -1 x the objective row at the call
 };
 
+// One LP of a ragged batch: where it lives in the batch's arrays, and its geometry
+struct BatchShape {           // 64 B per LP
+    int64_t t_off, b_off, c_off;   // its tableau in T (doubles), its basis, its row of the cost buffer
+    int32_t m, ncols;
+    int32_t ld;               // the tableau's row pitch in device memory, (ncols + 63) & ~63
+    int32_t pitch, txs;       // as BatchGeo's
+    int32_t nact;             // columns 1..nact are priced by k_batch_solve
+    int32_t art_first;        // of the last two-phase / Big-M call
+    int32_t pad[3];
+};
+static_assert(sizeof(BatchShape) == 64, "BatchShape is 64 bytes");
+
 struct BatchGeo {
-    double  *T;               // count x (m + nobj) x ld
-    int64_t *basis;           // count x m
+    double  *T;               // count x (m + nobj) x ld (ragged: LP q at shape[q].t_off)
+    int64_t *basis;           // count x m (ragged: LP q at shape[q].b_off)
     BatchLP *lp;              // count
     int32_t *logk, *logr;     // count x logcap, or null
     int32_t *running;         // LPs still RUNNING after this launch
@@ -98,7 +118,54 @@ struct BatchGeo {
     int32_t  pitch;           // TIER_LDS: row pitch in LDS (doubles, odd)
     int32_t  txs;             // update tile: 1 << txs lanes along a row, 256 >> txs rows at a time
     int32_t  nobj;            // objective rows: 1, or 2 for a Big-M batch (M part in row m, real part in row m + 1)
+    const BatchShape *shape;  // ragged: one record per LP (then ld, m, ncols, nact, pitch, txs above are not read); else null
+    const int32_t *order;     // ragged: workgroup w of this launch owns LP order[w]
 };
+
+// The LP of a workgroup and its geometry: the batch's one shape and LP =
+// workgroup, or the LP's BatchShape record
+struct LpGeo {
+    int64_t lp, t_off, b_off, c_off, m, ncols, ld, nact, art_first;
+    int32_t pitch, txs;
+};
+
+// the LP that workgroup blockIdx.x of a solve launch owns
+template <bool RG>
+__device__ __forceinline__ int64_t lp_index(const BatchGeo &g) {
+    return RG ? (int64_t)g.order[blockIdx.x] : (int64_t)blockIdx.x;
+}
+
+// geometry of LP `lp` (uniform in the workgroup); nobj and art_first are the caller's for a uniform batch
+template <bool RG>
+__device__ __forceinline__ LpGeo lp_geo(const BatchGeo &g, int64_t lp, int64_t nobj, int64_t art_first) {
+    LpGeo s;
+    s.lp = lp;
+    if (RG) {
+        const BatchShape r = g.shape[lp];
+        s.t_off = r.t_off;
+        s.b_off = r.b_off;
+        s.c_off = r.c_off;
+        s.m = r.m;
+        s.ncols = r.ncols;
+        s.ld = r.ld;
+        s.nact = r.nact;
+        s.art_first = r.art_first;
+        s.pitch = r.pitch;
+        s.txs = r.txs;
+    } else {
+        s.t_off = lp * (g.m + nobj) * g.ld;
+        s.b_off = lp * g.m;
+        s.c_off = lp * (g.ncols - 1);
+        s.m = g.m;
+        s.ncols = g.ncols;
+        s.ld = g.ld;
+        s.nact = g.nact;
+        s.art_first = art_first;
+        s.pitch = g.pitch;
+        s.txs = g.txs;
+    }
+    return s;
+}
 
 // ------------------------------------------------------------------------
 // generator: LP b = lpo_generate(n, seed + b, kind), one block per row
@@ -169,11 +236,13 @@ __global__ void k_batch_begin_two_phase(BatchLP *lp, int64_t count, int64_t budg
 }
 
 // dual feasibility of every LP: bad[0] = the first LP with a d_j < -eps_opt
+// (workgroup b looks at LP b, whatever the order of the solve launches)
 __global__ __launch_bounds__(kBlock) void k_batch_dual_check(BatchGeo g, unsigned long long *bad) {
     const int64_t b = blockIdx.x;
-    const double *obj = g.T + (b * (g.m + 1) + g.m) * g.ld;
+    const LpGeo s = g.shape ? lp_geo<true>(g, b, 1, 0) : lp_geo<false>(g, b, 1, 0);
+    const double *obj = g.T + s.t_off + s.m * s.ld;
     bool any = false;
-    for (int64_t j = 1 + threadIdx.x; j <= g.nact; j += kBlock) any |= obj[j] < -g.eps_opt;
+    for (int64_t j = 1 + threadIdx.x; j <= s.nact; j += kBlock) any |= obj[j] < -g.eps_opt;
     if (any) atomicMin(bad, (unsigned long long)b);
 }
 
@@ -226,29 +295,29 @@ struct BatchView {
     int64_t logcap, m, rows, ncols;
     int tid, tx, ty, j0, i0;  // update tile coordinates (BatchGeo::txs)
 
-    static __device__ __forceinline__ BatchView make(const BatchGeo &g, int64_t rows) {
+    // the LDS layout is this LP's own: the launch's dynamic LDS is an upper bound of it
+    static __device__ __forceinline__ BatchView make(const BatchGeo &g, const LpGeo &s, int64_t rows) {
         extern __shared__ double smem[];
-        const int64_t b = blockIdx.x;
         BatchView v;
-        v.gT = g.T + b * rows * g.ld;
-        v.ld = g.ld;
-        v.tp = TIER == TIER_LDS ? (int64_t)g.pitch : g.ld;
+        v.gT = g.T + s.t_off;
+        v.ld = s.ld;
+        v.tp = TIER == TIER_LDS ? (int64_t)s.pitch : s.ld;
         v.T = TIER == TIER_LDS ? smem : v.gT;
-        v.gB = g.basis + b * g.m;
+        v.gB = g.basis + s.b_off;
         v.sP = TIER == TIER_LDS ? smem + rows * v.tp : smem;
-        v.sC = v.sP + g.ncols;
+        v.sC = v.sP + s.ncols;
         v.sB = (int32_t *)(v.sC + rows);
-        v.logk = g.logk ? g.logk + b * g.logcap : nullptr;
-        v.logr = g.logk ? g.logr + b * g.logcap : nullptr;
+        v.logk = g.logk ? g.logk + s.lp * g.logcap : nullptr;
+        v.logr = g.logk ? g.logr + s.lp * g.logcap : nullptr;
         v.logcap = g.logcap;
-        v.m = g.m;
+        v.m = s.m;
         v.rows = rows;
-        v.ncols = g.ncols;
+        v.ncols = s.ncols;
         v.tid = threadIdx.x;
-        v.tx = 1 << g.txs;
-        v.ty = kBlock >> g.txs;
+        v.tx = 1 << s.txs;
+        v.ty = kBlock >> s.txs;
         v.j0 = v.tid & (v.tx - 1);
-        v.i0 = v.tid >> g.txs;
+        v.i0 = v.tid >> s.txs;
         return v;
     }
 
@@ -462,11 +531,13 @@ __device__ __forceinline__ void batch_write_back(const BatchGeo &g, const BatchV
 // ------------------------------------------------------------------------
 // the pivot loop of one LP (lpo.c lpo_solve, lpo_solve_dual)
 // ------------------------------------------------------------------------
-template <int MODE, int TIER>
+template <int MODE, int TIER, bool RG = false>
 __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
-    BatchLP *lp = g.lp + blockIdx.x;
+    const int64_t lpi = lp_index<RG>(g);
+    BatchLP *lp = g.lp + lpi;
     if (lp->status != RUNNING) return;            // finished in an earlier launch (or call): uniform
-    const BatchView<TIER> v = BatchView<TIER>::make(g, g.m + 1);
+    const LpGeo s = lp_geo<RG>(g, lpi, 1, 0);
+    const BatchView<TIER> v = BatchView<TIER>::make(g, s, s.m + 1);
     int32_t pst = lp->pstatus;
     int64_t pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
     v.load();
@@ -475,10 +546,10 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
     int64_t work = 0;
     for (;;) {
         if constexpr (MODE != MODE_DUAL) {
-            auto price = [&] { return batch_price<MODE>(v.T + v.m * v.tp, g.nact, g.eps_opt, v.tid); };
+            auto price = [&] { return batch_price<MODE>(v.T + v.m * v.tp, s.nact, g.eps_opt, v.tid); };
             status = batch_primal_step<MODE>(v, price, g.eps_piv, budget, g.chunk - work, pivots, last_k, last_r);
         } else {
-            status = batch_dual_step(v, g.nact, g.eps_piv, g.eps_opt, budget, g.chunk - work, pivots, last_k, last_r);
+            status = batch_dual_step(v, s.nact, g.eps_piv, g.eps_opt, budget, g.chunk - work, pivots, last_k, last_r);
         }
         if (status != STEP_APPLIED) break;
         pivots++;
@@ -500,13 +571,15 @@ __global__ __launch_bounds__(kBlock) void k_batch_solve(BatchGeo g) {
 // is one unit, and a launch ends in front of the unit that would exceed
 // g.chunk. `budget` is the oracle's: phase I may apply max_pivots pivots,
 // phase II max(0, max_pivots - pivots of the LP); drive-outs are not charged.
-template <int RULE, int TIER>
+template <int RULE, int TIER, bool RG = false>
 __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase t) {
-    BatchLP *lp = g.lp + blockIdx.x;
+    const int64_t lpi = lp_index<RG>(g);
+    BatchLP *lp = g.lp + lpi;
     if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
-    const BatchView<TIER> v = BatchView<TIER>::make(g, g.m + 1);
-    const int64_t m = g.m, ncols = g.ncols, af = t.art_first, chunk = g.chunk;
-    double *cost = t.cost + (int64_t)blockIdx.x * (ncols - 1);
+    const LpGeo s = lp_geo<RG>(g, lpi, 1, t.art_first);
+    const BatchView<TIER> v = BatchView<TIER>::make(g, s, s.m + 1);
+    const int64_t m = s.m, ncols = s.ncols, af = s.art_first, chunk = g.chunk;
+    double *cost = t.cost + s.c_off;
     int32_t phase = lp->phase, pst = lp->pstatus;
     int64_t cursor = lp->cursor, pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
     v.load();
@@ -602,13 +675,15 @@ __global__ __launch_bounds__(kBlock) void k_batch_two_phase(BatchGeo g, TwoPhase
 // from row m + 1 when save_cost); lp->phase is PH_OBJ1 until the objective
 // rows are set and PH_LOOP1 from then on, so a launch that ends in front of
 // any unit is resumed bitwise by the next.
-template <int RULE, int TIER>
+template <int RULE, int TIER, bool RG = false>
 __global__ __launch_bounds__(kBlock) void k_batch_big_m(BatchGeo g, TwoPhase t) {
-    BatchLP *lp = g.lp + blockIdx.x;
+    const int64_t lpi = lp_index<RG>(g);
+    BatchLP *lp = g.lp + lpi;
     if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
-    const BatchView<TIER> v = BatchView<TIER>::make(g, g.m + 2);
-    const int64_t m = g.m, ncols = g.ncols, af = t.art_first, chunk = g.chunk;
-    double *cost = t.cost + (int64_t)blockIdx.x * (ncols - 1);
+    const LpGeo s = lp_geo<RG>(g, lpi, 2, t.art_first);
+    const BatchView<TIER> v = BatchView<TIER>::make(g, s, s.m + 2);
+    const int64_t m = s.m, ncols = s.ncols, af = s.art_first, chunk = g.chunk;
+    double *cost = t.cost + s.c_off;
     int32_t phase = lp->phase, pst = lp->pstatus;
     int64_t pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
     v.load();
@@ -649,14 +724,16 @@ __global__ __launch_bounds__(kBlock) void k_batch_big_m(BatchGeo g, TwoPhase t) 
 
 // lpo_set_objective on every LP, costs as k_batch_two_phase's (count x N)
 __global__ __launch_bounds__(kBlock) void k_batch_set_objective(BatchGeo g, const double *costs) {
-    const int64_t b = blockIdx.x, m = g.m;
-    double *T = g.T + b * (m + 1) * g.ld;
-    const int64_t *gB = g.basis + b * m;
-    const double *cost = costs + b * (g.ncols - 1);
-    for (int64_t j = threadIdx.x; j < g.ncols; j += kBlock) {
+    const int64_t b = blockIdx.x;
+    const LpGeo s = g.shape ? lp_geo<true>(g, b, 1, 0) : lp_geo<false>(g, b, 1, 0);
+    const int64_t m = s.m, ld = s.ld;
+    double *T = g.T + s.t_off;
+    const int64_t *gB = g.basis + s.b_off;
+    const double *cost = costs + s.c_off;
+    for (int64_t j = threadIdx.x; j < s.ncols; j += kBlock) {
         double acc = 0.0;
-        for (int64_t i = 0; i < m; i++) acc = fma(gB[i] >= 1 ? cost[gB[i] - 1] : 0.0, T[i * g.ld + j], acc);
-        T[m * g.ld + j] = j == 0 ? acc : acc - cost[j - 1];
+        for (int64_t i = 0; i < m; i++) acc = fma(gB[i] >= 1 ? cost[gB[i] - 1] : 0.0, T[i * ld + j], acc);
+        T[m * ld + j] = j == 0 ? acc : acc - cost[j - 1];
     }
     if (threadIdx.x == 0) g.lp[b].status = g.lp[b].pstatus = RUNNING;
 }
@@ -689,7 +766,25 @@ struct lpg_batch {
     double *cost = nullptr;       // count x N real costs of two-phase and Big-M calls / set_objective (allocated on first use)
     hipStream_t stream = nullptr;
     char err[512] = {0};
+    // A round of a solve call is one launch per group: LPs order[first .. first + count)
+    // with `lds` bytes of dynamic LDS on `tier`, its count of running LPs in running[slot].
+    // A uniform batch is one group of all its LPs.
+    struct Group {
+        int64_t first, count, lds;
+        int tier, slot;
+    };
+    std::vector<Group> groups;
+    // a ragged batch (lpg_batch_create_ragged): m, ncols, ld and lds above are the
+    // largest of any LP, tier is TIER_GLOBAL if any LP is on it
+    bool ragged = false;
+    std::vector<BatchShape> shape;            // the records, as in dshape
+    std::vector<lpg_batch_shape_t> pub;       // what lpg_batch_shape reports, packed offsets included
+    int64_t t_total = 0, b_total = 0, c_total = 0;   // doubles of T, entries of basis, doubles of cost
+    BatchShape *dshape = nullptr;
+    int32_t *dorder = nullptr;
 };
+
+constexpr int kBatchSlots = 2;                // ints behind lpg_batch::running: group 0 (global tier) and group 1 (LDS tier)
 
 namespace {
 
@@ -734,6 +829,16 @@ BatchGeo bgeo(const lpg_batch *b) {
     g.pitch = b->pitch;
     g.txs = b->txs;
     g.nobj = b->nobj;
+    g.shape = b->dshape;
+    g.order = b->dorder;
+    return g;
+}
+
+// the geometry a launch of group `gr` sees: its slice of the order, its counter
+BatchGeo bgeo(const lpg_batch *b, const lpg_batch::Group &gr) {
+    BatchGeo g = bgeo(b);
+    if (g.order) g.order += gr.first;
+    g.running += gr.slot;
     return g;
 }
 
@@ -774,10 +879,10 @@ int alloc_log(lpg_batch *b, int64_t cap) {
 // which solver a call runs
 enum Method { M_PRIMAL, M_DUAL, M_TWO_PHASE, M_BIG_M };
 
-// one launch of solve kernel K (`name` for the error message), one workgroup
-// per LP; its dynamic LDS limit is raised once per device
+// one launch of solve kernel K (`name` for the error message) on group `gr`,
+// one workgroup per LP; its dynamic LDS limit is raised once per device
 template <auto K, class... Args>
-int launch_lp(lpg_batch *b, const char *name, const Args &...args) {
+int launch_lp(lpg_batch *b, const lpg_batch::Group &gr, const char *name, const Args &...args) {
     static std::atomic<unsigned long long> attr{0};
     const int dev = b->device & 63;
     if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
@@ -787,29 +892,43 @@ int launch_lp(lpg_batch *b, const char *name, const Args &...args) {
         }
         attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
     }
-    hipLaunchKernelGGL(K, dim3((unsigned)b->count), dim3(kBlock), (size_t)b->lds, b->stream, bgeo(b), args...);
+    hipLaunchKernelGGL(K, dim3((unsigned)gr.count), dim3(kBlock), (size_t)gr.lds, b->stream, bgeo(b, gr), args...);
     return 0;
 }
 
-template <int TIER>
-int launch_tier(lpg_batch *b, Method method, int rule, const TwoPhase &t) {
+template <int TIER, bool RG>
+int launch_tier(lpg_batch *b, const lpg_batch::Group &gr, Method method, int rule, const TwoPhase &t) {
     const bool bland = rule == RULE_BLAND;
     switch (method) {
-    case M_DUAL: return launch_lp<k_batch_solve<MODE_DUAL, TIER>>(b, "k_batch_solve");
+    case M_DUAL: return launch_lp<k_batch_solve<MODE_DUAL, TIER, RG>>(b, gr, "k_batch_solve");
     case M_PRIMAL:
-        return bland ? launch_lp<k_batch_solve<RULE_BLAND, TIER>>(b, "k_batch_solve")
-                     : launch_lp<k_batch_solve<RULE_DANTZIG, TIER>>(b, "k_batch_solve");
+        return bland ? launch_lp<k_batch_solve<RULE_BLAND, TIER, RG>>(b, gr, "k_batch_solve")
+                     : launch_lp<k_batch_solve<RULE_DANTZIG, TIER, RG>>(b, gr, "k_batch_solve");
     case M_TWO_PHASE:
-        return bland ? launch_lp<k_batch_two_phase<RULE_BLAND, TIER>>(b, "k_batch_two_phase", t)
-                     : launch_lp<k_batch_two_phase<RULE_DANTZIG, TIER>>(b, "k_batch_two_phase", t);
+        return bland ? launch_lp<k_batch_two_phase<RULE_BLAND, TIER, RG>>(b, gr, "k_batch_two_phase", t)
+                     : launch_lp<k_batch_two_phase<RULE_DANTZIG, TIER, RG>>(b, gr, "k_batch_two_phase", t);
     default:
-        return bland ? launch_lp<k_batch_big_m<RULE_BLAND, TIER>>(b, "k_batch_big_m", t)
-                     : launch_lp<k_batch_big_m<RULE_DANTZIG, TIER>>(b, "k_batch_big_m", t);
+        return bland ? launch_lp<k_batch_big_m<RULE_BLAND, TIER, RG>>(b, gr, "k_batch_big_m", t)
+                     : launch_lp<k_batch_big_m<RULE_DANTZIG, TIER, RG>>(b, gr, "k_batch_big_m", t);
     }
 }
 
-int launch_solve(lpg_batch *b, Method method, int rule, const TwoPhase &t) {
-    return b->tier == TIER_LDS ? launch_tier<TIER_LDS>(b, method, rule, t) : launch_tier<TIER_GLOBAL>(b, method, rule, t);
+int launch_solve(lpg_batch *b, const lpg_batch::Group &gr, Method method, int rule, const TwoPhase &t) {
+    if (b->ragged)
+        return gr.tier == TIER_LDS ? launch_tier<TIER_LDS, true>(b, gr, method, rule, t)
+                                   : launch_tier<TIER_GLOBAL, true>(b, gr, method, rule, t);
+    return gr.tier == TIER_LDS ? launch_tier<TIER_LDS, false>(b, gr, method, rule, t)
+                               : launch_tier<TIER_GLOBAL, false>(b, gr, method, rule, t);
+}
+
+// what the calls of the other layout answer: a uniform-layout call on a ragged
+// batch, or a packed / _ragged call on a batch of one shape
+int wrong_layout(lpg_batch *b, const char *call, const char *other) {
+    if (b->ragged)
+        return bfail(b, LPG_ERR_STATE, "%s: this is a ragged batch (lpg_batch_create_ragged), whose LPs have no common "
+                                       "shape; use %s; nothing has moved or pivoted", call, other);
+    return bfail(b, LPG_ERR_STATE, "%s: this batch has one shape (lpg_batch_create, lpg_batch_create_big_m); use %s; "
+                                   "nothing has moved or pivoted", call, other);
 }
 
 // what a Big-M batch refuses (and a plain batch, for lpg_batch_solve_big_m)
@@ -821,15 +940,19 @@ int wrong_kind(lpg_batch *b, const char *call) {
                                    "lpg_batch_create_big_m; nothing has pivoted", call);
 }
 
-// the batch's count x N cost buffer, filled from the host's (pitch ld_cost) when given
+// the batch's count x N cost buffer, filled from the host's (pitch ld_cost) when given;
+// ragged: the packed costs, ncols - 1 per LP, the same on both sides
 int stage_costs(lpg_batch *b, const double *cost, int64_t ld_cost) {
     const int64_t N = b->ncols - 1;
-    if (!b->cost && hipMalloc(&b->cost, (size_t)b->count * (size_t)N * sizeof(double)) != hipSuccess) {
+    const size_t total = b->ragged ? (size_t)b->c_total : (size_t)b->count * (size_t)N;
+    if (!b->cost && hipMalloc(&b->cost, total * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         b->cost = nullptr;
         return bfail(b, LPG_ERR_OOM, "hipMalloc(costs of %lld LPs) failed", (long long)b->count);
     }
-    if (cost)
+    if (cost && b->ragged)
+        BHIPCHK(b, hipMemcpyAsync(b->cost, cost, total * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    else if (cost)
         BHIPCHK(b, hipMemcpy2DAsync(b->cost, (size_t)N * sizeof(double), cost, (size_t)ld_cost * sizeof(double),
                                     (size_t)N * sizeof(double), (size_t)b->count, hipMemcpyHostToDevice, b->stream));
     if (cost) BHIPCHK(b, hipStreamSynchronize(b->stream));        // the caller's array is free again
@@ -870,17 +993,25 @@ int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_res
                            max_pivots, method == M_DUAL ? 1 : 0);
     BHIPCHK(b, hipGetLastError());
     b->pivoted = true;
+    // a round: one launch per group that still has running LPs; the counters are
+    // reset once before it and read once after it
+    int32_t live[kBatchSlots];
+    const size_t nslots = (size_t)b->groups.back().slot + 1;
     for (int64_t it = 0;; it++) {
-        int32_t running = 0;
-        BHIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
-        if (int rc = launch_solve(b, method, rule, t)) return rc;
-        BHIPCHK(b, hipGetLastError());
-        BHIPCHK(b, hipMemcpyAsync(&running, b->running, sizeof running, hipMemcpyDeviceToHost, b->stream));
+        BHIPCHK(b, hipMemsetAsync(b->running, 0, nslots * sizeof(int32_t), b->stream));
+        for (const lpg_batch::Group &gr : b->groups) {
+            if (it > 0 && live[gr.slot] == 0) continue;
+            if (int rc = launch_solve(b, gr, method, rule, t)) return rc;
+            BHIPCHK(b, hipGetLastError());
+        }
+        BHIPCHK(b, hipMemcpyAsync(live, b->running, nslots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
         BHIPCHK(b, hipStreamSynchronize(b->stream));
+        int64_t running = 0;
+        for (size_t q = 0; q < nslots; q++) running += live[q];
         if (running == 0) break;
         if (it + 1 >= max_launches)
-            return bfail(b, LPG_ERR_DEVICE, "lpg_batch: %d LPs still running after %lld launches of %d pivots", running,
-                         (long long)(it + 1), b->chunk);
+            return bfail(b, LPG_ERR_DEVICE, "lpg_batch: %lld LPs still running after %lld rounds of %d pivots",
+                         (long long)running, (long long)(it + 1), b->chunk);
     }
     if (out) {
         std::vector<BatchLP> h((size_t)b->count);
@@ -902,6 +1033,8 @@ int solve_artificial(lpg_batch *b, Method method, const char *call, int64_t art_
                      int64_t max_pivots, int rule, lpg_result *out) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
     if ((b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
+    if (b->ragged)
+        return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m_ragged" : "lpg_batch_solve_two_phase_ragged");
     const int64_t N = b->ncols - 1;
     if (art_first < 2 || art_first > N)
         return bfail(b, LPG_ERR_ARG, "%s: art_first %lld outside 2..%lld", call, (long long)art_first, (long long)N);
@@ -921,6 +1054,41 @@ int solve_artificial(lpg_batch *b, Method method, const char *call, int64_t art_
     return batch_run(b, max_pivots, method, rule, out, t);
 }
 
+// the records of a ragged batch to the device (after nact or art_first changed)
+int push_shapes(lpg_batch *b) {
+    BHIPCHK(b, hipMemcpy(b->dshape, b->shape.data(), b->shape.size() * sizeof(BatchShape), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// lpg_batch_solve_two_phase_ragged and lpg_batch_solve_big_m_ragged: solve_artificial with one
+// art_first per LP and packed costs
+int solve_artificial_ragged(lpg_batch *b, Method method, const char *call, const int64_t *art_first, const double *cost,
+                            int64_t max_pivots, int rule, lpg_result *out) {
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if ((b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
+    if (!b->ragged) return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m" : "lpg_batch_solve_two_phase");
+    if (!art_first) return bfail(b, LPG_ERR_ARG, "%s: art_first is NULL", call);
+    for (int64_t q = 0; q < b->count; q++)
+        if (art_first[q] < 2 || art_first[q] > b->shape[(size_t)q].ncols - 1)
+            return bfail(b, LPG_ERR_ARG, "%s: art_first %lld of LP %lld outside 2..%lld", call, (long long)art_first[q],
+                         (long long)q, (long long)(b->shape[(size_t)q].ncols - 1));
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = stage_costs(b, cost, 0)) return rc;
+    for (int64_t q = 0; q < b->count; q++) {
+        b->shape[(size_t)q].art_first = (int32_t)art_first[q];
+        // two-phase: what phase II prices, and what a later lpg_batch_solve goes on with
+        if (method == M_TWO_PHASE) b->shape[(size_t)q].nact = (int32_t)art_first[q] - 1;
+    }
+    if (int rc = push_shapes(b)) return rc;
+    TwoPhase t{};
+    t.cost = b->cost;
+    t.max_pivots = max_pivots;
+    t.save_cost = cost ? 0 : 1;
+    return batch_run(b, max_pivots, method, rule, out, t);
+}
+
 // lpg_batch_generate and lpg_batch_generate_artificial once the arguments are checked
 int generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
     BHIPCHK(b, hipSetDevice(b->device));
@@ -930,6 +1098,97 @@ int generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
     BHIPCHK(b, hipGetLastError());
     BHIPCHK(b, hipStreamSynchronize(b->stream));
     b->pivoted = false;
+    return 0;
+}
+
+// env LPG_BATCH_CHUNK into *chunk (0: not set)
+int env_chunk(int *chunk) {
+    *chunk = 0;
+    if (const char *ce = getenv("LPG_BATCH_CHUNK")) {
+        const long long v = atoll(ce);
+        if (v < 1 || v > (1 << 20))
+            return bfail(nullptr, LPG_ERR_ARG, "LPG_BATCH_CHUNK=%s out of range [1, %d]", ce, 1 << 20);
+        *chunk = (int)v;
+    }
+    return 0;
+}
+
+bool env_is(const char *name, const char *value) {
+    const char *e = getenv(name);
+    return e && !strcmp(e, value);
+}
+
+// a launch stays bounded in time as well as in pivots: the LDS tier spends
+// microseconds per pivot; a global-tier workgroup streams its tableau twice
+// per pivot at some tens of GB/s, so large tableaus get fewer pivots per
+// launch (about 0.1 s at 50 GB/s). rows x ncols: the largest global-tier LP.
+int default_chunk(bool any_global, int64_t rows, int64_t ncols) {
+    if (!any_global) return kBatchChunk;
+    const double per_pivot = 16.0 * (double)rows * (double)ncols / 50e9;
+    return (int)std::min<double>(kBatchChunk, std::max(16.0, 0.1 / per_pivot));
+}
+
+int txs_of(int64_t ncols) {
+    int txs = 0;
+    while ((1 << txs) < ncols && txs < 8) txs++;
+    return txs;
+}
+
+// The device side of a batch whose host fields are set (t_total, b_total, the
+// log capacity `logcap`, for a ragged batch shape and `order`): allocations,
+// stream, zero tableaus (the padding columns stay zero for good), slack-less
+// bases, fresh states. On failure the batch is destroyed.
+int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector<int32_t> &order) {
+    auto die = [&](int code) {
+        snprintf(g_berr, sizeof g_berr, "%s", b->err);
+        lpg_batch_destroy(b);
+        return code;
+    };
+    const int64_t count = b->count;
+    hipError_t e = hipSetDevice(b->device);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipSetDevice(%d): %s", b->device, hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    const size_t tbytes = (size_t)b->t_total * sizeof(double), bbytes = (size_t)b->b_total * sizeof(int64_t);
+    if (hipMalloc(&b->T, tbytes) != hipSuccess || hipMalloc(&b->basis, bbytes) != hipSuccess ||
+        hipMalloc(&b->lp, (size_t)count * sizeof(BatchLP)) != hipSuccess ||
+        hipMalloc(&b->running, kBatchSlots * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&b->bad, sizeof(unsigned long long)) != hipSuccess ||
+        (b->ragged && (hipMalloc(&b->dshape, (size_t)count * sizeof(BatchShape)) != hipSuccess ||
+                       hipMalloc(&b->dorder, (size_t)count * sizeof(int32_t)) != hipSuccess))) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_OOM, "hipMalloc(batch of %lld tableaus, %zu bytes) failed", (long long)count, tbytes);
+        return die(LPG_ERR_OOM);
+    }
+    if (int rc = alloc_log(b, logcap)) return die(rc);
+    if ((e = hipStreamCreate(&b->stream)) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    if (hipMemsetAsync(b->T, 0, tbytes, b->stream) != hipSuccess ||
+        hipMemsetAsync(b->basis, 0, bbytes, b->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipMemset failed");
+        return die(LPG_ERR_DEVICE);
+    }
+    if (b->ragged &&
+        (hipMemcpyAsync(b->dshape, b->shape.data(), (size_t)count * sizeof(BatchShape), hipMemcpyHostToDevice, b->stream) !=
+             hipSuccess ||
+         hipMemcpyAsync(b->dorder, order.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, b->stream) !=
+             hipSuccess)) {
+        (void)hipGetLastError();
+        bfail(b, LPG_ERR_DEVICE, "hipMemcpy(shapes of %lld LPs) failed", (long long)count);
+        return die(LPG_ERR_DEVICE);
+    }
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, count);
+    if ((e = hipStreamSynchronize(b->stream)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) {
+        bfail(b, LPG_ERR_DEVICE, "batch setup: %s", hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    *out = b;
     return 0;
 }
 
@@ -954,12 +1213,7 @@ int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t 
         return bfail(nullptr, LPG_ERR_ARG, "%s: count * (m + %d) = %lld x %lld exceeds 2^31 - 1", call, nobj,
                      (long long)count, (long long)rows);
     int chunk = 0;
-    if (const char *ce = getenv("LPG_BATCH_CHUNK")) {
-        const long long v = atoll(ce);
-        if (v < 1 || v > (1 << 20))
-            return bfail(nullptr, LPG_ERR_ARG, "LPG_BATCH_CHUNK=%s out of range [1, %d]", ce, 1 << 20);
-        chunk = (int)v;
-    }
+    if (int rc = env_chunk(&chunk)) return rc;
     lpg_batch *b = new lpg_batch();
     b->device = device;
     b->count = count;
@@ -969,64 +1223,122 @@ int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t 
     b->nact = ncols - 1;
     b->nobj = nobj;
     b->flags = flags;
-    const char *te = getenv("LPG_BATCH_TIER");
-    const bool force_global = te && !strcmp(te, "global");
+    const bool force_global = env_is("LPG_BATCH_TIER", "global");
     b->tier = (!force_global && lds_bytes(TIER_LDS, m, ncols, nobj) <= kBatchMaxLds) ? TIER_LDS : TIER_GLOBAL;
     b->lds = lds_bytes(b->tier, m, ncols, nobj);
     b->pitch = (int)(ncols | 1);
-    while ((1 << b->txs) < ncols && b->txs < 8) b->txs++;
-    if (!chunk) {
-        // a launch stays bounded in time as well as in pivots: the LDS tier
-        // spends microseconds per pivot; a global-tier workgroup streams its
-        // tableau twice per pivot at some tens of GB/s, so large tableaus get
-        // fewer pivots per launch (about 0.1 s at 50 GB/s)
-        chunk = kBatchChunk;
-        if (b->tier == TIER_GLOBAL) {
-            const double per_pivot = 16.0 * (double)rows * (double)ncols / 50e9;
-            chunk = (int)std::min<double>(kBatchChunk, std::max(16.0, 0.1 / per_pivot));
+    b->txs = txs_of(ncols);
+    b->chunk = chunk ? chunk : default_chunk(b->tier == TIER_GLOBAL, rows, ncols);
+    b->groups.push_back({0, count, b->lds, b->tier, 0});
+    b->t_total = count * rows * ld;
+    b->b_total = count * m;
+    return batch_alloc(out, b, 2 * (m + ncols), {});
+}
+
+int ragged_create(lpg_batch **out, int device, int64_t count, const int64_t *m, const int64_t *ncols, int nobj,
+                  uint32_t flags) {
+    const char *call = "lpg_batch_create_ragged";
+    if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!m || !ncols) return bfail(nullptr, LPG_ERR_ARG, "%s: %s is NULL", call, !m ? "m" : "ncols");
+    if (count < 1) return bfail(nullptr, LPG_ERR_ARG, "%s: count = %lld (need count >= 1)", call, (long long)count);
+    if (nobj != 1 && nobj != 2)
+        return bfail(nullptr, LPG_ERR_ARG, "%s: nobj = %d (1: a plain batch, 2: a Big-M batch)", call, nobj);
+    if (flags & ~(uint32_t)LPG_FLAG_NO_LOG)
+        return bfail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_FLAG_NO_LOG only: nobj = 2 makes a Big-M "
+                                           "batch; no eager or no-skip batches)", call, flags);
+    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+    int64_t sum_rows = 0;
+    for (int64_t q = 0; q < count; q++) {
+        if (m[q] < 1) return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: m = %lld (need m >= 1)", call, (long long)q, (long long)m[q]);
+        if (ncols[q] < 2)
+            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: ncols = %lld (need ncols >= 2)", call, (long long)q,
+                         (long long)ncols[q]);
+        if (m[q] + nobj > LPG_BATCH_MAX_DIM)
+            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: m + %d = %lld exceeds %d; a tableau this large belongs to "
+                                               "lpg_create", call, (long long)q, nobj, (long long)(m[q] + nobj), LPG_BATCH_MAX_DIM);
+        if (ncols[q] > LPG_BATCH_MAX_DIM)
+            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: ncols = %lld exceeds %d; a tableau this large belongs to "
+                                               "lpg_create", call, (long long)q, (long long)ncols[q], LPG_BATCH_MAX_DIM);
+        sum_rows += m[q] + nobj;
+        if (sum_rows > (int64_t)0x7fffffff)
+            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: the rows of LPs 0..%lld (m + %d each) exceed 2^31 - 1", call,
+                         (long long)q, (long long)q, nobj);
+    }
+    int chunk = 0;
+    if (int rc = env_chunk(&chunk)) return rc;
+    const bool force_global = env_is("LPG_BATCH_TIER", "global");
+
+    lpg_batch *b = new lpg_batch();
+    b->device = device;
+    b->count = count;
+    b->nobj = nobj;
+    b->flags = flags;
+    b->ragged = true;
+    b->tier = TIER_LDS;
+    b->shape.resize((size_t)count);
+    b->pub.resize((size_t)count);
+    int64_t big_global = 0, grows = 0, gncols = 0, pt = 0;
+    for (int64_t q = 0; q < count; q++) {
+        BatchShape &s = b->shape[(size_t)q];
+        lpg_batch_shape_t &p = b->pub[(size_t)q];
+        const int64_t rows = m[q] + nobj, ld = (ncols[q] + 63) & ~(int64_t)63;
+        s = BatchShape{};
+        s.t_off = b->t_total;
+        s.b_off = b->b_total;
+        s.c_off = b->c_total;
+        s.m = (int32_t)m[q];
+        s.ncols = (int32_t)ncols[q];
+        s.ld = (int32_t)ld;
+        s.pitch = (int32_t)(ncols[q] | 1);
+        s.txs = txs_of(ncols[q]);
+        s.nact = (int32_t)ncols[q] - 1;
+        s.art_first = (int32_t)ncols[q];           // no artificial column until a call names one
+        p.m = m[q];
+        p.ncols = ncols[q];
+        p.ld = ld;
+        p.tier = (!force_global && lds_bytes(TIER_LDS, m[q], ncols[q], nobj) <= kBatchMaxLds) ? TIER_LDS : TIER_GLOBAL;
+        p.lds_bytes = lds_bytes(p.tier, m[q], ncols[q], nobj);
+        p.group = p.tier == TIER_GLOBAL ? 0 : 1;
+        p.tableau_offset = pt;
+        p.basis_offset = b->b_total;
+        p.cost_offset = b->c_total;
+        pt += rows * ncols[q];
+        b->t_total += rows * ld;
+        b->b_total += m[q];
+        b->c_total += ncols[q] - 1;
+        b->m = std::max(b->m, m[q]);
+        b->ncols = std::max(b->ncols, ncols[q]);
+        b->ld = std::max(b->ld, ld);
+        b->lds = std::max(b->lds, p.lds_bytes);
+        if (p.tier == TIER_GLOBAL) {
+            b->tier = TIER_GLOBAL;
+            if (rows * ncols[q] > big_global) big_global = rows * ncols[q], grows = rows, gncols = ncols[q];
         }
     }
-    b->chunk = chunk;
-    auto die = [&](int code) {
-        snprintf(g_berr, sizeof g_berr, "%s", b->err);
-        lpg_batch_destroy(b);
-        return code;
-    };
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
-        return die(LPG_ERR_DEVICE);
+    b->nact = b->ncols - 1;
+    b->chunk = chunk ? chunk : default_chunk(b->tier == TIER_GLOBAL, grows, gncols);
+    // the order of the workgroups: the global-tier group, then the LDS-tier group
+    // (launched with the LDS of its largest LP; one group per occupancy class was
+    // measured and not kept), in a group the LPs with the most
+    // update work first, so that the round's tail is short
+    std::vector<int32_t> order((size_t)count);
+    for (int64_t q = 0; q < count; q++) order[(size_t)q] = (int32_t)q;
+    std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+        const lpg_batch_shape_t &px = b->pub[(size_t)x], &py = b->pub[(size_t)y];
+        if (px.group != py.group) return px.group < py.group;
+        const int64_t wx = (px.m + nobj) * px.ncols, wy = (py.m + nobj) * py.ncols;
+        return wx != wy ? wx > wy : x < y;
+    });
+    for (int64_t w = 0; w < count; w++) {
+        const lpg_batch_shape_t &p = b->pub[(size_t)order[(size_t)w]];
+        if (b->groups.empty() || b->groups.back().slot != p.group) b->groups.push_back({w, 0, 0, p.tier, p.group});
+        b->groups.back().count++;
+        b->groups.back().lds = std::max(b->groups.back().lds, p.lds_bytes);
     }
-    const size_t tbytes = (size_t)count * (size_t)rows * (size_t)ld * sizeof(double);
-    if (hipMalloc(&b->T, tbytes) != hipSuccess || hipMalloc(&b->basis, (size_t)count * (size_t)m * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&b->lp, (size_t)count * sizeof(BatchLP)) != hipSuccess ||
-        hipMalloc(&b->running, sizeof(int32_t)) != hipSuccess || hipMalloc(&b->bad, sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        bfail(b, LPG_ERR_OOM, "hipMalloc(batch of %lld tableaus, %zu bytes) failed", (long long)count, tbytes);
-        return die(LPG_ERR_OOM);
-    }
-    if (int rc = alloc_log(b, 2 * (m + ncols))) return die(rc);
-    if ((e = hipStreamCreate(&b->stream)) != hipSuccess) {
-        (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
-        return die(LPG_ERR_DEVICE);
-    }
-    // zero tableaus (the padding columns stay zero for good), slack-less bases, fresh states
-    if (hipMemsetAsync(b->T, 0, tbytes, b->stream) != hipSuccess ||
-        hipMemsetAsync(b->basis, 0, (size_t)count * (size_t)m * sizeof(int64_t), b->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipMemset failed");
-        return die(LPG_ERR_DEVICE);
-    }
-    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, count);
-    if ((e = hipStreamSynchronize(b->stream)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) {
-        bfail(b, LPG_ERR_DEVICE, "batch setup: %s", hipGetErrorString(e));
-        return die(LPG_ERR_DEVICE);
-    }
-    *out = b;
-    return 0;
+    return batch_alloc(out, b, 2 * (b->m + b->ncols), order);
 }
+
 
 }  // namespace
 
@@ -1057,6 +1369,8 @@ void lpg_batch_destroy(lpg_batch *b) {
     if (b->running) (void)hipFree(b->running);
     if (b->bad) (void)hipFree(b->bad);
     if (b->cost) (void)hipFree(b->cost);
+    if (b->dshape) (void)hipFree(b->dshape);
+    if (b->dorder) (void)hipFree(b->dorder);
     delete b;
 }
 
@@ -1071,12 +1385,118 @@ int lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *o) {
     o->lds_bytes = b->lds;
     o->log_capacity = b->logcap;
     o->nobj = b->nobj;
-    o->pad = 0;
+    o->pad = b->ragged ? 1 : 0;
     return 0;
+}
+
+int lpg_batch_create_ragged(lpg_batch **out, int device, int64_t count, const int64_t *m, const int64_t *ncols, int nobj,
+                            uint32_t flags) {
+    return ragged_create(out, device, count, m, ncols, nobj, flags);
+}
+
+int lpg_batch_shape(const lpg_batch *cb, int64_t lp, lpg_batch_shape_t *o) {
+    lpg_batch *b = const_cast<lpg_batch *>(cb);
+    if (!b || !o) return bfail(b, LPG_ERR_ARG, "lpg_batch_shape: NULL argument");
+    if (!b->ragged) return wrong_layout(b, "lpg_batch_shape", "lpg_batch_info");
+    if (lp < 0 || lp >= b->count)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_shape: LP %lld outside the batch of %lld", (long long)lp, (long long)b->count);
+    *o = b->pub[(size_t)lp];
+    return 0;
+}
+
+int lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, const int64_t *basis) {
+    if (!b || !tableaus) return bfail(b, LPG_ERR_ARG, "lpg_batch_load_packed: NULL argument");
+    if (!b->ragged) return wrong_layout(b, "lpg_batch_load_packed", "lpg_batch_load");
+    if (int rc = range_ok(b, "lpg_batch_load_packed", first, n)) return rc;
+    if (n == 0) return 0;
+    const BatchShape &s0 = b->shape[(size_t)first], &s1 = b->shape[(size_t)(first + n - 1)];
+    if (basis)
+        for (int64_t q = first; q < first + n; q++) {
+            const BatchShape &s = b->shape[(size_t)q];
+            for (int64_t i = 0; i < s.m; i++) {
+                const int64_t k = basis[s.b_off - s0.b_off + i];
+                if (k < 1 || k >= s.ncols)
+                    return bfail(b, LPG_ERR_ARG, "lpg_batch_load_packed: basis[%lld] of LP %lld out of range 1..%lld",
+                                 (long long)i, (long long)q, (long long)(s.ncols - 1));
+            }
+        }
+    BHIPCHK(b, hipSetDevice(b->device));
+    // the LPs' device images are back to back: build them on the host (rows at
+    // pitch ld, zero padding) and move them in one copy
+    const int64_t doubles = s1.t_off + (int64_t)(s1.m + b->nobj) * s1.ld - s0.t_off;
+    std::vector<double> img((size_t)doubles, 0.0);
+    const double *src = tableaus;
+    for (int64_t q = first; q < first + n; q++) {
+        const BatchShape &s = b->shape[(size_t)q];
+        double *dst = img.data() + (s.t_off - s0.t_off);
+        for (int64_t i = 0; i < s.m + b->nobj; i++, src += s.ncols, dst += s.ld) memcpy(dst, src, (size_t)s.ncols * sizeof(double));
+    }
+    BHIPCHK(b, hipMemcpyAsync(b->T + s0.t_off, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (basis)
+        BHIPCHK(b, hipMemcpyAsync(b->basis + s0.b_off, basis, (size_t)(s1.b_off + s1.m - s0.b_off) * sizeof(int64_t),
+                                  hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(n)), dim3(kBlock), 0, b->stream, b->lp, first, n);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    if (first == 0 && n == b->count) b->pivoted = false;
+    return 0;
+}
+
+int lpg_batch_get_rows_packed(lpg_batch *b, int64_t first, int64_t n, double *out) {
+    if (!b || !out) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows_packed: NULL argument");
+    if (!b->ragged) return wrong_layout(b, "lpg_batch_get_rows_packed", "lpg_batch_get_rows");
+    if (int rc = range_ok(b, "lpg_batch_get_rows_packed", first, n)) return rc;
+    if (n == 0) return 0;
+    BHIPCHK(b, hipSetDevice(b->device));
+    const BatchShape &s0 = b->shape[(size_t)first], &s1 = b->shape[(size_t)(first + n - 1)];
+    std::vector<double> img((size_t)(s1.t_off + (int64_t)(s1.m + b->nobj) * s1.ld - s0.t_off));
+    BHIPCHK(b, hipMemcpyAsync(img.data(), b->T + s0.t_off, img.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    for (int64_t q = first; q < first + n; q++) {
+        const BatchShape &s = b->shape[(size_t)q];
+        const double *src = img.data() + (s.t_off - s0.t_off);
+        for (int64_t i = 0; i < s.m + b->nobj; i++, src += s.ld, out += s.ncols) memcpy(out, src, (size_t)s.ncols * sizeof(double));
+    }
+    return 0;
+}
+
+int lpg_batch_get_basis_packed(lpg_batch *b, int64_t first, int64_t n, int64_t *basis) {
+    if (!b || !basis) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_basis_packed: NULL argument");
+    if (!b->ragged) return wrong_layout(b, "lpg_batch_get_basis_packed", "lpg_batch_get_basis");
+    if (int rc = range_ok(b, "lpg_batch_get_basis_packed", first, n)) return rc;
+    if (n == 0) return 0;
+    BHIPCHK(b, hipSetDevice(b->device));
+    const BatchShape &s0 = b->shape[(size_t)first], &s1 = b->shape[(size_t)(first + n - 1)];
+    BHIPCHK(b, hipMemcpy(basis, b->basis + s0.b_off, (size_t)(s1.b_off + s1.m - s0.b_off) * sizeof(int64_t),
+                         hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lpg_batch_set_objective_packed(lpg_batch *b, const double *cost) {
+    if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective_packed: NULL argument");
+    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_set_objective_packed");
+    if (!b->ragged) return wrong_layout(b, "lpg_batch_set_objective_packed", "lpg_batch_set_objective");
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = stage_costs(b, cost, 0)) return rc;
+    hipLaunchKernelGGL(k_batch_set_objective, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b), b->cost);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int lpg_batch_solve_two_phase_ragged(lpg_batch *b, const int64_t *art_first, const double *cost, int64_t max_pivots,
+                                     int rule, lpg_result *out) {
+    return solve_artificial_ragged(b, M_TWO_PHASE, "lpg_batch_solve_two_phase_ragged", art_first, cost, max_pivots, rule, out);
+}
+
+int lpg_batch_solve_big_m_ragged(lpg_batch *b, const int64_t *art_first, const double *cost, int64_t max_pivots, int rule,
+                                 lpg_result *out) {
+    return solve_artificial_ragged(b, M_BIG_M, "lpg_batch_solve_big_m_ragged", art_first, cost, max_pivots, rule, out);
 }
 
 int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, int64_t ld, const int64_t *basis) {
     if (!b || !tableaus) return bfail(b, LPG_ERR_ARG, "lpg_batch_load: NULL argument");
+    if (b->ragged) return wrong_layout(b, "lpg_batch_load", "lpg_batch_load_packed");
     if (int rc = range_ok(b, "lpg_batch_load", first, n)) return rc;
     if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_load: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
     if (basis)
@@ -1104,6 +1524,7 @@ int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableau
 int lpg_batch_generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (b->nobj == 2) return wrong_kind(b, "lpg_batch_generate");
+    if (b->ragged) return wrong_layout(b, "lpg_batch_generate", "lpg_batch_load_packed (a ragged batch has no generator)");
     if (n < 1 || b->ncols != n + b->m + 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
                      (long long)(n + b->m + 1));
@@ -1121,6 +1542,8 @@ int lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt) {
 
 int lpg_batch_set_active_columns(lpg_batch *b, int64_t nact) {
     if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_set_active_columns");
+    if (b && b->ragged)
+        return wrong_layout(b, "lpg_batch_set_active_columns", "lpg_batch_solve_two_phase_ragged, which sets them per LP");
     if (!b || nact < 1 || nact > b->ncols - 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_set_active_columns: nact out of range 1..N");
     b->nact = nact;
@@ -1161,6 +1584,7 @@ int lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, i
 int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
     if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: NULL argument");
     if (b->nobj == 2) return wrong_kind(b, "lpg_batch_set_objective");
+    if (b->ragged) return wrong_layout(b, "lpg_batch_set_objective", "lpg_batch_set_objective_packed");
     if (ld_cost < b->ncols - 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: ld_cost %lld < N = %lld", (long long)ld_cost,
                      (long long)(b->ncols - 1));
@@ -1174,6 +1598,8 @@ int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
 
 int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_t *art_first) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (b->ragged)
+        return wrong_layout(b, "lpg_batch_generate_artificial", "lpg_batch_load_packed (a ragged batch has no generator)");
     if (n < 1 || b->ncols != n + b->m + 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate_artificial: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
                      (long long)(n + b->m + 1));
@@ -1184,6 +1610,7 @@ int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_
 
 int lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld) {
     if (!b || !out) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: NULL argument");
+    if (b->ragged) return wrong_layout(b, "lpg_batch_get_rows", "lpg_batch_get_rows_packed");
     if (int rc = range_ok(b, "lpg_batch_get_rows", first, n)) return rc;
     if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
     if (n == 0) return 0;
@@ -1197,6 +1624,7 @@ int lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int6
 
 int lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis) {
     if (!b || !basis) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_basis: NULL argument");
+    if (b->ragged) return wrong_layout(b, "lpg_batch_get_basis", "lpg_batch_get_basis_packed");
     if (int rc = range_ok(b, "lpg_batch_get_basis", first, n)) return rc;
     if (n == 0) return 0;
     BHIPCHK(b, hipSetDevice(b->device));

@@ -295,7 +295,17 @@ class BatchEngine:
     """`count` LPs of one shape, each an (m+1) x ncols tableau, solved in one
     launch with one workgroup per LP (include/lpg.h, "batches"). ``big_m=True``:
     a Big-M batch, (m+2) x ncols tableaus (row m the M part, row m + 1 the real
-    part of the objective), solved by solve_big_m only."""
+    part of the objective), solved by solve_big_m only.
+
+    ``BatchEngine.ragged(shapes)`` makes a ragged batch instead: LP q has its own
+    (m, ncols) = shapes[q], and the solve calls still run all of them in one
+    round of launches, every LP bit for bit what it computes alone. Its methods
+    take and return one array per LP (RaggedBatchEngine)."""
+
+    @staticmethod
+    def ragged(shapes, device: int = 0, big_m: bool = False, flags: int = 0, lib=None) -> "RaggedBatchEngine":
+        """A batch of len(shapes) LPs, LP q of shapes[q] = (m, ncols)."""
+        return RaggedBatchEngine(shapes, device=device, big_m=big_m, flags=flags, lib=lib)
 
     def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None, big_m: bool = False):
         self.lib = lib if lib is not None else L.load()
@@ -439,3 +449,116 @@ class BatchEngine:
         self._check(self.lib.lpg_batch_get_log(self._b, lp, k.ctypes.data_as(L.c_int64_p),
                                                r.ctypes.data_as(L.c_int64_p), n), "lpg_batch_get_log")
         return k[:n], r[:n]
+
+
+class RaggedBatchEngine(BatchEngine):
+    """BatchEngine.ragged(shapes): LPs of different shapes in one batch
+    (include/lpg.h, "ragged batches"). LP q is an (m_q + nobj) x ncols_q tableau;
+    load, set_objective and the artificial solves take one array per LP, get_rows
+    and get_basis return one per LP; solve, solve_dual, reserve_log, set_tolerances,
+    get_log and info are BatchEngine's (info reports the largest m, ncols, ld and
+    lds_bytes). The packing to and from the C ABI's flat arrays happens here."""
+
+    def __init__(self, shapes, device: int = 0, big_m: bool = False, flags: int = 0, lib=None):
+        self.lib = lib if lib is not None else L.load()
+        self._b = ctypes.c_void_p()
+        try:
+            self.shapes = [(int(m), int(nc)) for m, nc in shapes]
+        except (TypeError, ValueError) as e:
+            raise LPGError(f"BatchEngine.ragged: shapes must be a list of (m, ncols): {e}") from None
+        self.count, self.nobj = len(self.shapes), 2 if big_m else 1
+        ms = np.array([m for m, _ in self.shapes], dtype=np.int64)
+        ncs = np.array([nc for _, nc in self.shapes], dtype=np.int64)
+        rc = self.lib.lpg_batch_create_ragged(ctypes.byref(self._b), device, self.count, ms.ctypes.data_as(L.c_int64_p),
+                                              ncs.ctypes.data_as(L.c_int64_p), self.nobj, flags)
+        if rc != 0:
+            raise LPGError(f"lpg_batch_create_ragged rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+        self.m, self.ncols = int(ms.max()), int(ncs.max())
+
+    def shape(self, lp: int) -> L.BatchShape:
+        s = L.BatchShape()
+        self._check(self.lib.lpg_batch_shape(self._b, lp, ctypes.byref(s)), "lpg_batch_shape")
+        return s
+
+    def _flat(self, arrays, what, shape_of, dtype):
+        """One array per LP, each of shape_of(m, ncols), flattened LP after LP."""
+        arrays = list(arrays)
+        if len(arrays) != self.count:
+            raise LPGError(f"{what}: {len(arrays)} arrays for {self.count} LPs")
+        parts = []
+        for q, (a, (m, nc)) in enumerate(zip(arrays, self.shapes)):
+            a = np.asarray(a, dtype=dtype)
+            if a.shape != shape_of(m, nc):
+                raise LPGError(f"{what}: LP {q} has shape {a.shape}, want {shape_of(m, nc)}")
+            parts.append(a.ravel())
+        return np.ascontiguousarray(np.concatenate(parts))
+
+    def _split(self, flat, shape_of):
+        out, at = [], 0
+        for m, nc in self.shapes:
+            shp = shape_of(m, nc)
+            n = int(np.prod(shp))
+            out.append(flat[at:at + n].reshape(shp).copy())
+            at += n
+        return out
+
+    def load(self, tableaus, bases=None):
+        """tableaus[q]: [m_q + nobj, ncols_q] (objective row(s) last), bases[q]: [m_q]; the whole batch."""
+        T = self._flat(tableaus, "load", lambda m, nc: (m + self.nobj, nc), np.float64)
+        bp = None
+        if bases is not None:
+            bas = self._flat(bases, "load (bases)", lambda m, nc: (m,), np.int64)
+            bp = bas.ctypes.data_as(L.c_int64_p)
+        self._check(self.lib.lpg_batch_load_packed(self._b, 0, self.count, T.ctypes.data_as(L.c_double_p), bp),
+                    "lpg_batch_load_packed")
+
+    def _packed_costs(self, costs, what):
+        if costs is None:
+            return None, None
+        c = self._flat(costs, what, lambda m, nc: (nc - 1,), np.float64)
+        return c, c.ctypes.data_as(L.c_double_p)
+
+    def _art(self, art_first, what):
+        af = np.ascontiguousarray(art_first, dtype=np.int64)
+        if af.shape != (self.count,):
+            raise LPGError(f"{what}: art_first of shape {af.shape}, want [{self.count}]")
+        return af
+
+    def solve_two_phase(self, art_first, costs=None, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> list:
+        """BatchEngine.solve_two_phase with art_first[q] and costs[q] ([ncols_q - 1]) per LP; costs None: -1 x each
+        LP's objective row. Afterwards LP q's active columns are 1..art_first[q]-1."""
+        af = self._art(art_first, "solve_two_phase")
+        keep, cp = self._packed_costs(costs, "solve_two_phase")
+        r = (L.Result * self.count)()
+        self._check(self.lib.lpg_batch_solve_two_phase_ragged(self._b, af.ctypes.data_as(L.c_int64_p), cp, max_pivots, rule,
+                                                              r), "lpg_batch_solve_two_phase_ragged")
+        del keep
+        return [_res(x) for x in r]
+
+    def solve_big_m(self, art_first, costs=None, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> list:
+        """BatchEngine.solve_big_m with art_first[q] and costs[q] per LP."""
+        af = self._art(art_first, "solve_big_m")
+        keep, cp = self._packed_costs(costs, "solve_big_m")
+        r = (L.Result * self.count)()
+        self._check(self.lib.lpg_batch_solve_big_m_ragged(self._b, af.ctypes.data_as(L.c_int64_p), cp, max_pivots, rule, r),
+                    "lpg_batch_solve_big_m_ragged")
+        del keep
+        return [_res(x) for x in r]
+
+    def set_objective(self, costs):
+        """Engine.set_objective on every LP; costs[q]: [ncols_q - 1]."""
+        keep, cp = self._packed_costs(costs, "set_objective")
+        self._check(self.lib.lpg_batch_set_objective_packed(self._b, cp), "lpg_batch_set_objective_packed")
+        del keep
+
+    def get_rows(self) -> list:
+        flat = np.zeros(sum((m + self.nobj) * nc for m, nc in self.shapes), dtype=np.float64)
+        self._check(self.lib.lpg_batch_get_rows_packed(self._b, 0, self.count, flat.ctypes.data_as(L.c_double_p)),
+                    "lpg_batch_get_rows_packed")
+        return self._split(flat, lambda m, nc: (m + self.nobj, nc))
+
+    def get_basis(self) -> list:
+        flat = np.zeros(sum(m for m, _ in self.shapes), dtype=np.int64)
+        self._check(self.lib.lpg_batch_get_basis_packed(self._b, 0, self.count, flat.ctypes.data_as(L.c_int64_p)),
+                    "lpg_batch_get_basis_packed")
+        return self._split(flat, lambda m, nc: (m,))

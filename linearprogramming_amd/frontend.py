@@ -710,7 +710,7 @@ def _groups(arrays) -> dict:
     return groups
 
 
-def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase") -> list:
+def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase", ragged: bool = False) -> list:
     """solve(sm, method=method) for every SMatrix of ``sms``, the models of one
     shape (m, nc0, nlack) together in one BatchEngine: one launch per group
     instead of one engine per model. ``method`` as solve()'s: "two_phase" or
@@ -721,7 +721,9 @@ def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase") -
     an unknown method for "two_phase", any other method is a FrontendError: a
     misspelt method would otherwise cost a whole batch. The result list is in
     input order and each entry equals solve(sm, method=method) field by field,
-    floats bit for bit."""
+    floats bit for bit. ``ragged=True`` gives the same results from at most two
+    ragged batches whatever the shapes: one for the models the plain primal or
+    the dual simplex solves, one for those that need artificials."""
     from . import _lib as L
     from .engine import BatchEngine
     if method not in ("two_phase", "big_m", "dual"):
@@ -739,6 +741,37 @@ def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase") -
                 raise FrontendError(f"dual simplex: the slack basis of model {idx} is not dual feasible (a positive "
                                     "max-form cost)")
     out = [None] * len(sms)
+    if ragged:
+        plain = [idx for idx, a in enumerate(arrays) if method == "dual" or a[4] == 0]
+        lacking = [idx for idx, a in enumerate(arrays) if method != "dual" and a[4] > 0]
+        for members, art in ((plain, False), (lacking, True)):
+            if not members:
+                continue
+            bigm = art and method == "big_m"
+            tabs = []
+            for idx in members:
+                m, nc = arrays[idx][0].shape
+                T = np.zeros((m + (2 if bigm else 1), nc), dtype=np.float64)
+                T[:m] = arrays[idx][0]
+                tabs.append(T)
+            costs = [arrays[idx][2][:-1] for idx in members]
+            with BatchEngine.ragged([arrays[idx][0].shape for idx in members], device=device, big_m=bigm) as e:
+                e.load(tabs, [arrays[idx][1] for idx in members])
+                if not art:
+                    e.set_objective(costs)
+                    res, used = (e.solve_dual(), "dual") if method == "dual" else (e.solve(rule=rule), "primal")
+                elif bigm:
+                    res, used = e.solve_big_m([arrays[idx][3] for idx in members], costs, rule=rule), "big_m"
+                else:
+                    res, used = e.solve_two_phase([arrays[idx][3] for idx in members], costs, rule=rule), "two_phase"
+                rows, bas = e.get_rows(), e.get_basis()
+            for q, idx in enumerate(members):
+                r, m = res[q], arrays[idx][0].shape[0]
+                sol = LPSolution(r.status_name, int(r.pivots), method=used)
+                if r.status == L.OPTIMAL:
+                    _readout(sms[idx], sol, r.objective, rows[q][:m, 0], bas[q], arrays[idx][0].shape[1])
+                out[idx] = sol
+        return out
     for (m, nc0, nlack), members in _groups(arrays).items():
         nc = nc0 + nlack
         bigm = method == "big_m" and nlack > 0

@@ -2,6 +2,18 @@
 """Batch solver vs a loop of single-LP engines: B generated LPs of one shape.
 
     python tools/batch_bench.py --m 64 --n 128 --batch 1024 [--repeats 5] [--kind dense] [--out FILE]
+    python tools/batch_bench.py --ragged --batch 1024 --shapes 64 [--dims 4 64] [--extra 130x130] [--out FILE]
+
+--ragged: B dense LPs over K distinct seeded shapes (m and n drawn from
+--dims; --extra MxN adds one LP of that shape), their tableaus made by a
+uniform BatchEngine.generate per shape and read back (not timed). Then three
+ways to solve them, each timed from the creation of its batches to the last
+result (and, as a second figure, its solve calls alone): (i) one ragged batch;
+(ii) one uniform batch per shape, created, loaded and solved in turn, which is
+frontend.solve_batch(ragged=False); (iii) every LP zero-padded to the largest
+shape in one uniform batch. One warm-up of each, then `repeats` timed runs,
+the legs alternating; they must agree on every status and pivot count, else
+the run fails.
 
 --kind artificial: the generator's artificial LPs (equality rows with
 artificial unit columns) by the two-phase method, (a) generate_artificial +
@@ -45,10 +57,128 @@ DS_READ_B64_BPC, DS_WRITE_B64_BPC = 256.0, 85.0      # bytes per clock and CU
 KINDS = {"dense": 0, "degenerate": 1, "artificial": 2}
 
 
+def ragged_main(a) -> int:
+    import random
+
+    import numpy as np
+
+    import linearprogramming_amd as lpg
+    rnd = random.Random(a.seed)
+    lo, hi = a.dims
+    shapes = set()
+    while len(shapes) < a.shapes:
+        shapes.add((rnd.randint(lo, hi), rnd.randint(lo, hi)))
+    shapes = sorted(shapes)
+    of_lp = shapes + [shapes[rnd.randrange(len(shapes))] for _ in range(a.batch - len(shapes))]
+    rnd.shuffle(of_lp)
+    if a.extra:
+        em, en = (int(x) for x in a.extra.lower().split("x"))
+        of_lp.insert(len(of_lp) // 2, (em, en))
+    B = len(of_lp)
+    rule, flags = 1 if a.rule == "bland" else 0, lpg._lib.FLAG_NO_LOG
+    members = {}
+    for q, sh in enumerate(of_lp):
+        members.setdefault(sh, []).append(q)
+    tabs, bases = [None] * B, [None] * B
+    for si, ((m, n), idx) in enumerate(members.items()):                 # set-up, not timed
+        with lpg.BatchEngine(len(idx), m, n + m + 1, device=a.device, flags=flags) as e:
+            e.generate(n, a.seed + 4096 * si, 0)
+            T, bs = e.get_rows(), e.get_basis()
+        for k, q in enumerate(idx):
+            tabs[q], bases[q] = T[k], bs[k]
+    M, NC = max(m for m, _ in of_lp), max(n + m + 1 for m, n in of_lp)
+    budget = 50 * (M + NC)
+    Tpad, bpad = np.zeros((B, M + 1, NC)), np.ones((B, M), dtype=np.int64)
+    for q, (m, n) in enumerate(of_lp):                                    # zero rows and columns never pivot
+        nc = n + m + 1
+        Tpad[q, :m, :nc], Tpad[q, M, :nc], bpad[q, :m] = tabs[q][:m], tabs[q][m], bases[q]
+    group_T = {sh: np.array([tabs[q] for q in idx]) for sh, idx in members.items()}
+    group_b = {sh: np.array([bases[q] for q in idx]) for sh, idx in members.items()}
+
+    def leg_ragged():
+        t0 = time.perf_counter()
+        with lpg.BatchEngine.ragged([(m, n + m + 1) for m, n in of_lp], device=a.device, flags=flags) as e:
+            e.load(tabs, bases)
+            t1 = time.perf_counter()
+            res = e.solve(budget, rule)
+            t2 = time.perf_counter()
+            groups = len({e.shape(q).group for q in range(B)}) if not leg_ragged.groups else leg_ragged.groups
+        leg_ragged.groups = groups
+        return time.perf_counter() - t0, t2 - t1, [(r.status, r.pivots) for r in res]
+    leg_ragged.groups = 0
+
+    def leg_per_shape():
+        out, ts = [None] * B, 0.0
+        t0 = time.perf_counter()
+        for (m, n), idx in members.items():
+            with lpg.BatchEngine(len(idx), m, n + m + 1, device=a.device, flags=flags) as e:
+                e.load(group_T[(m, n)], group_b[(m, n)])
+                t1 = time.perf_counter()
+                res = e.solve(budget, rule)
+                ts += time.perf_counter() - t1
+            for k, q in enumerate(idx):
+                out[q] = (res[k].status, res[k].pivots)
+        return time.perf_counter() - t0, ts, out
+
+    def leg_padded():
+        t0 = time.perf_counter()
+        with lpg.BatchEngine(B, M, NC, device=a.device, flags=flags) as e:
+            e.load(Tpad, bpad)
+            t1 = time.perf_counter()
+            res = e.solve(budget, rule)
+            t2 = time.perf_counter()
+            tier = "lds" if e.info.tier == lpg.BATCH_TIER_LDS else "global"
+        leg_padded.tier = tier
+        return time.perf_counter() - t0, t2 - t1, [(r.status, r.pivots) for r in res]
+
+    legs = {"ragged": leg_ragged, "per_shape": leg_per_shape, "padded": leg_padded}
+    want = None
+    for name, leg in legs.items():                                        # warm-up, and the agreement check
+        _, _, got = leg()
+        want = got if want is None else want
+        if got != want:
+            bad = [q for q, (x, y) in enumerate(zip(got, want)) if x != y]
+            print(json.dumps({"error": f"{name} and ragged disagree", "first": bad[0], "shape": of_lp[bad[0]],
+                              name: got[bad[0]], "ragged": want[bad[0]], "count": len(bad)}))
+            return 1
+    total, solve = {k: [] for k in legs}, {k: [] for k in legs}
+    for _ in range(a.repeats):
+        for name, leg in legs.items():
+            t, ts, got = leg()
+            assert got == want, name
+            total[name].append(t)
+            solve[name].append(ts)
+    pivots = sum(p for _, p in want)
+
+    def rates(ts):
+        med = statistics.median(ts)
+        return {"seconds_median": med, "seconds_min": min(ts), "seconds_max": max(ts), "lps_per_s": B / med}
+
+    line = {"bench": "ragged", "batch": B, "shapes": len(members), "dims": [lo, hi], "extra": a.extra, "rule": a.rule,
+            "max_m": M, "max_ncols": NC, "pivots": pivots, "repeats": a.repeats,
+            "launch_groups": leg_ragged.groups,
+            "padded_tier": leg_padded.tier, "build_stamp": lpg._lib.build_stamp}
+    for name in legs:
+        line[name] = {"create_load_solve": rates(total[name]), "solve_only": rates(solve[name])}
+    for other in ("per_shape", "padded"):
+        line[f"ragged_slowest_below_fastest_{other}"] = max(total["ragged"]) < min(total[other])
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--m", type=int, required=True)
-    ap.add_argument("--n", type=int, required=True)
+    ap.add_argument("--m", type=int)
+    ap.add_argument("--n", type=int)
+    ap.add_argument("--ragged", action="store_true", help="B LPs over --shapes distinct shapes: ragged vs per-shape vs padded")
+    ap.add_argument("--shapes", type=int, default=64)
+    ap.add_argument("--dims", type=int, nargs=2, default=[4, 64], metavar=("LO", "HI"))
+    ap.add_argument("--extra", default=None, metavar="MxN", help="--ragged: one more LP of this shape")
     ap.add_argument("--batch", type=int, required=True)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--seed", type=int, default=20220518)
@@ -60,6 +190,12 @@ def main() -> int:
     ap.add_argument("--no-loop", action="store_true", help="time (a) only (e.g. to compare the tiers: LPG_BATCH_TIER=global)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.ragged:
+        if a.shapes < 1 or a.batch < a.shapes or (a.dims[1] - a.dims[0] + 1) ** 2 < a.shapes:
+            ap.error("--ragged needs 1 <= --shapes <= --batch and that many shapes within --dims")
+        return ragged_main(a)
+    if a.m is None or a.n is None:
+        ap.error("--m and --n are required without --ragged")
 
     import linearprogramming_amd as lpg
     m, n, B, nc = a.m, a.n, a.batch, a.n + a.m + 1

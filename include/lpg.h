@@ -506,6 +506,59 @@ int  lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis)
 /* LP lp's log: copies min(recorded, max) pivots, returns the number recorded
  * (= min(pivots, log capacity)), < 0 on error. */
 int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int64_t max);
+/* LP lp's active columns 1..*nact (what lpg_batch_solve and _solve_dual price)
+ * and, for a ragged batch, the art_first recorded by its last two-phase or
+ * Big-M call (a batch of one shape: ncols); either pointer may be NULL. */
+int  lpg_batch_active_columns(const lpg_batch *b, int64_t lp, int64_t *nact, int64_t *art_first);
+
+/* ---- branching: the step between two levels of a branch-and-bound tree ----
+ *
+ * The node LPs of a tree are the LPs of a batch. lpg_batch_branch_select picks
+ * the branching variable of every LP (lpg_batch.hip k_batch_branch_select, one
+ * workgroup per LP over its basis), lpg_batch_branch makes the batch of the
+ * children on the device (k_batch_branch, one workgroup per child): a child is
+ * its parent's tableau in the parent's current basis plus one bound row, so it
+ * is dual feasible wherever the parent was LPG_OPTIMAL and
+ * lpg_batch_solve_dual(child) re-optimises it. No tableau crosses the host.
+ * Both calls work on batches of one shape and on ragged ones and refuse a
+ * Big-M batch (LPG_ERR_STATE). Only floor, ceil, one subtraction, one
+ * negation and comparisons are used, so a host restatement reproduces both
+ * bit for bit (tests/branch_cases.py). */
+#define LPG_BRANCH_MOST_FRACTIONAL 0   /* largest distance to an integer; ties -> smallest column */
+#define LPG_BRANCH_FIRST           1   /* smallest fractional integer column */
+typedef struct { int64_t row, col; double value; } lpg_branch_t;   /* row = col = -1: every integer column integral */
+/* out[q] for every LP q: column j (1-based) is integer-constrained in LP q iff
+ * j <= nmask && mask[q * ld_mask + j - 1] (ld_mask == 0: one mask of nmask
+ * bytes for every LP; else ld_mask >= nmask). Of the rows i whose basic
+ * column is integer-constrained, with v = T[i][0], f = v - floor(v) and
+ * dist = min(f, 1 - f), those with dist > int_tol are candidates; `rule`
+ * picks one, out[q] = (its row, its basic column, v). LPG_ERR_ARG before any
+ * device work: NULL arguments, nmask outside 1..ncols-1 (ragged: the largest
+ * ncols), 0 < ld_mask < nmask, int_tol not in [0, 0.5), another rule. */
+int  lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask,
+                             double int_tol, int rule, lpg_branch_t *out /* count */);
+/* *child = a new batch of n LPs: child c is LP src[c] of `parent` with one
+ * more row and one more column, the bound x <= floor(v) (dir[c] = -1) or
+ * x >= ceil(v) (dir[c] = +1) on the variable x basic in row[c], v = T[row][0].
+ * With nact the source's active columns: columns 0..nact are copied, the new
+ * slack column is nact + 1 (zero in every other row, the objective row
+ * included, 1 in the new row), the source's columns beyond nact (the inert
+ * artificials of a two-phase solve) move right by one and basis entries
+ * beyond nact grow by one. Constraint rows 0..m-1 are copied, the new row is
+ * row m with basis[m] = nact + 1, the objective row becomes row m + 1. The
+ * new row is -T[row][j] with right-hand side floor(v) - v (dir -1) or
+ * +T[row][j] with v - ceil(v) (dir +1), the entry in x's own column exactly
+ * 0. The child's active columns are 1..nact+1 (a ragged child's recorded
+ * art_first grows by one as well); it inherits the parent's tolerances and
+ * flags; its LPs are fresh: LPG_RUNNING, no pivots, empty log. A parent of
+ * one shape gives a child of one shape (m + 1, ncols + 1), a ragged parent a
+ * ragged child. The parent is unchanged. Before any device work, with a
+ * message that names the first offending index: n < 1, NULL arrays, a src
+ * outside the parent, a row outside 0..m_src-1, a dir other than -1 / +1, a
+ * child dimension over LPG_BATCH_MAX_DIM (LPG_ERR_ARG); a Big-M parent
+ * (LPG_ERR_STATE). On any error *child is NULL. */
+int  lpg_batch_branch(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *row,
+                      const int8_t *dir);
 
 #ifdef __cplusplus
 }

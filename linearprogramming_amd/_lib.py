@@ -27,9 +27,12 @@ FLAG_EAGER = 0x8
 DEFER_MAX = 128
 BATCH_TIER_LDS, BATCH_TIER_GLOBAL = 0, 1
 BATCH_MAX_DIM = 8192
+BRANCH_MOST_FRACTIONAL, BRANCH_FIRST = 0, 1
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
+c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
+c_int8_p = ctypes.POINTER(ctypes.c_int8)
 
 
 class Result(ctypes.Structure):
@@ -65,6 +68,11 @@ class BatchShape(ctypes.Structure):
     _fields_ = [("m", ctypes.c_int64), ("ncols", ctypes.c_int64), ("ld", ctypes.c_int64),
                 ("tier", ctypes.c_int32), ("group", ctypes.c_int32), ("lds_bytes", ctypes.c_int64),
                 ("tableau_offset", ctypes.c_int64), ("basis_offset", ctypes.c_int64), ("cost_offset", ctypes.c_int64)]
+
+
+class Branch(ctypes.Structure):
+    """lpg_branch_t."""
+    _fields_ = [("row", ctypes.c_int64), ("col", ctypes.c_int64), ("value", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -152,6 +160,11 @@ PROTOTYPES = [
                                                         ctypes.c_int, ctypes.POINTER(Result)]),
     ("lpg_batch_solve_big_m_ragged", ctypes.c_int, [ctypes.c_void_p, c_int64_p, c_double_p, ctypes.c_int64,
                                                     ctypes.c_int, ctypes.POINTER(Result)]),
+    ("lpg_batch_active_columns", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p]),
+    ("lpg_batch_branch_select", ctypes.c_int, [ctypes.c_void_p, c_uint8_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                               ctypes.c_int, ctypes.POINTER(Branch)]),
+    ("lpg_batch_branch", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64, c_int64_p,
+                                        c_int64_p, c_int8_p]),
 ]
 
 

@@ -40,6 +40,12 @@
 // there on runs the code of a uniform batch. RG, the last template parameter
 // of the solve kernels, says which of the two a launch is: a uniform batch
 // runs the instantiations it ran before there were ragged ones.
+//
+// Branching (lpg_batch_branch_select, lpg_batch_branch): the step between two
+// levels of a branch-and-bound tree whose node LPs are a batch.
+// k_batch_branch_select picks every LP's branching row over its basis;
+// k_batch_branch makes the batch of the children, each its parent's tableau
+// plus one bound row and one slack column, by a copy in device memory.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -738,6 +744,125 @@ __global__ __launch_bounds__(kBlock) void k_batch_set_objective(BatchGeo g, cons
     if (threadIdx.x == 0) g.lp[b].status = g.lp[b].pstatus = RUNNING;
 }
 
+// ------------------------------------------------------------------------
+// branching (include/lpg.h, "branching"): the step between two levels of a
+// branch-and-bound tree, on the tableaus where the solve calls left them
+// ------------------------------------------------------------------------
+
+struct BranchPick {           // lpg_branch_t
+    int64_t row, col;
+    double value;
+};
+static_assert(sizeof(BranchPick) == sizeof(lpg_branch_t), "BranchPick is lpg_branch_t");
+
+// The branching row of LP blockIdx.x: over the rows whose basic column is
+// integer-constrained (mask, nmask bytes per LP at pitch ld_mask, 0: one for
+// all), the candidates are those with dist = min(f, 1 - f) > int_tol,
+// f = v - floor(v), v = T[i][0]. A candidate is a pricing partial (v = -dist
+// < 0, j = its column, pad = its row), so the block argmin of the solve
+// kernels picks it: RULE_DANTZIG the largest dist, ties -> the smallest
+// column; RULE_BLAND the smallest column (the basic columns of an LP differ).
+template <int RULE>
+__global__ __launch_bounds__(kBlock) void k_batch_branch_select(BatchGeo g, const uint8_t *mask, int64_t nmask, int64_t ld_mask,
+                                                                double int_tol, BranchPick *out) {
+    const int64_t q = blockIdx.x;
+    const LpGeo s = g.shape ? lp_geo<true>(g, q, 1, 0) : lp_geo<false>(g, q, 1, 0);
+    const double *T = g.T + s.t_off;
+    const int64_t *gB = g.basis + s.b_off;
+    const uint8_t *mk = mask + q * ld_mask;
+    PricePart pb{0.0, -1, 0, 0};
+    for (int64_t i = threadIdx.x; i < s.m; i += kBlock) {
+        const int64_t bj = gB[i];
+        const bool integer = (bj >= 1) & (bj <= nmask) && mk[bj - 1] != 0;
+        const double v = T[i * s.ld];
+        const double f = v - floor(v), f1 = 1.0 - f;
+        const double dist = f < f1 ? f : f1;
+        PricePart c{-dist, (integer & (dist > int_tol)) ? bj : -1, 0, (int32_t)i};
+        pp_take(pb, c, pp_better<RULE>(c, pb));
+    }
+    pb = block_argmin_pp<RULE>(pb);
+    if (threadIdx.x == 0) {
+        BranchPick o{-1, -1, 0.0};
+        if (pb.j >= 0) {
+            o.row = pb.pad;
+            o.col = pb.j;
+            o.value = T[(int64_t)pb.pad * s.ld];
+        }
+        out[q] = o;
+    }
+}
+
+struct BranchJob {            // child c of lpg_batch_branch: validated on the host
+    int32_t src, row, dir, pad;
+};
+
+// entry (i, j) of the child, j a column of the unshifted part (0..nact: the
+// parent's column j), from the parent's entry x of the source row: a copy, or
+// in the new row `m` one negation; its right-hand side and the zero in the
+// branching variable's own column are exact
+__device__ __forceinline__ double branch_entry(double x, bool newrow, int64_t j, int64_t bj, bool down, double rhs) {
+    if (!newrow) return x;
+    const double y = down ? -x : x;
+    return j == 0 ? rhs : (j == bj ? 0.0 : y);
+}
+
+// Child blockIdx.x of `c` from LP job.src of `p` (RG: both ragged, as the
+// parent is). A copy kernel: the parent's tableau is streamed from device memory
+// row by row into the child's rows at the child's pitch. Columns 0..nact keep
+// their place: both pitches are multiples of 64 doubles and both tableaus
+// start on one, so the even part of them moves as 16-byte loads and stores,
+// consecutive lanes on consecutive pairs of a row. The rest of a row (the new
+// slack column nact + 1, behind it the parent's columns nact + 1.. one to the
+// right) moves as doubles. The child's padding columns stay the zeros of its
+// allocation.
+template <bool RG>
+__global__ __launch_bounds__(kBlock) void k_batch_branch(BatchGeo p, BatchGeo c, const BranchJob *jobs) {
+    const BranchJob job = jobs[blockIdx.x];
+    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0), cs = lp_geo<RG>(c, blockIdx.x, 1, 0);
+    const double *pT = p.T + ps.t_off;
+    double *cT = c.T + cs.t_off;
+    const int64_t *pB = p.basis + ps.b_off;
+    int64_t *cB = c.basis + cs.b_off;
+    const int64_t m = ps.m, nc = ps.ncols, nact = ps.nact, pld = ps.ld, cld = cs.ld, r = job.row;
+    const bool down = job.dir < 0;
+    const double v = pT[r * pld];
+    const int64_t bj = pB[r];
+    const double rhs = down ? floor(v) - v : v - ceil(v);
+    const int tid = threadIdx.x;
+
+    // a tile of 1 << txs lanes along a row (enough for its pairs, 256 at the most) and 256 >> txs rows at a
+    // time: the row and column of a lane come from shifts, and a narrow LP still fills the workgroup.
+    // child row i comes from the parent's row i (i < m), `r` (the new row m) or m (the objective, now row m + 1)
+    const int npair = (int)((nact + 1) >> 1), w0 = 2 * npair;      // columns [0, w0) as pairs
+    int txs = 0;
+    while ((1 << txs) < npair && txs < 8) txs++;
+    const int tx = 1 << txs, ty = kBlock >> txs, j0 = tid & (tx - 1), i0 = tid >> txs;
+    for (int64_t i = i0; i < m + 2; i += ty) {
+        const int64_t si = i < m ? i : (i == m ? r : m);
+        const double *prow = pT + si * pld;
+        double *crow = cT + i * cld;
+        const bool newrow = i == m;
+        for (int j = 2 * j0; j < w0; j += 2 * tx) {
+            const d2 x = *(const d2 *)(prow + j);
+            d2 y;
+            y.x = branch_entry(x.x, newrow, j, bj, down, rhs);
+            y.y = branch_entry(x.y, newrow, j + 1, bj, down, rhs);
+            *(d2 *)(crow + j) = y;
+        }
+        // child columns [w0, nc]: at most one unshifted column, the slack, the shifted columns
+        for (int64_t j = w0 + j0; j <= nc; j += tx) {
+            double y;
+            if (j == nact + 1) y = newrow ? 1.0 : 0.0;
+            else {
+                const int64_t pj = j <= nact ? j : j - 1;
+                y = branch_entry(prow[pj], newrow, pj, bj, down, rhs);
+            }
+            crow[j] = y;
+        }
+    }
+    for (int64_t i = tid; i <= m; i += kBlock) cB[i] = i == m ? nact + 1 : (pB[i] > nact ? pB[i] + 1 : pB[i]);
+}
+
 }  // namespace lpg
 
 // ---------------------------------------------------------------------------
@@ -1339,6 +1464,139 @@ int ragged_create(lpg_batch **out, int device, int64_t count, const int64_t *m, 
     return batch_alloc(out, b, 2 * (b->m + b->ncols), order);
 }
 
+// m, ncols and active columns of LP q, whatever the layout
+int64_t lp_m(const lpg_batch *b, int64_t q) { return b->ragged ? b->shape[(size_t)q].m : b->m; }
+int64_t lp_ncols(const lpg_batch *b, int64_t q) { return b->ragged ? b->shape[(size_t)q].ncols : b->ncols; }
+int64_t lp_nact(const lpg_batch *b, int64_t q) { return b->ragged ? b->shape[(size_t)q].nact : b->nact; }
+
+// a device buffer of a branching call: freed when the call returns
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+int branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
+                  lpg_branch_t *out) {
+    const char *call = "lpg_batch_branch_select";
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (!mask || !out) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
+    if (b->nobj == 2) return wrong_kind(b, call);
+    if (nmask < 1 || nmask > b->ncols - 1)
+        return bfail(b, LPG_ERR_ARG, "%s: nmask %lld outside 1..%lld (the columns of the %s)", call, (long long)nmask,
+                     (long long)(b->ncols - 1), b->ragged ? "widest LP" : "batch");
+    if (ld_mask != 0 && ld_mask < nmask)
+        return bfail(b, LPG_ERR_ARG, "%s: ld_mask %lld < nmask %lld (0: one mask for every LP)", call, (long long)ld_mask,
+                     (long long)nmask);
+    if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
+    if (rule != LPG_BRANCH_MOST_FRACTIONAL && rule != LPG_BRANCH_FIRST) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    BHIPCHK(b, hipSetDevice(b->device));
+    // the masks packed at pitch nmask: the kernel reads mask[q * pitch + j - 1] for j <= nmask only
+    const int64_t nrows = ld_mask ? b->count : 1;
+    DevBuf dmask, dout;
+    if (hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess ||
+        hipMalloc(&dout.p, (size_t)b->count * sizeof(BranchPick)) != hipSuccess) {
+        (void)hipGetLastError();
+        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and picks of %lld LPs) failed", call, (long long)b->count);
+    }
+    BHIPCHK(b, hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask,
+                                (size_t)nrows, hipMemcpyHostToDevice, b->stream));
+    const int64_t pitch = ld_mask ? nmask : 0;
+    if (rule == LPG_BRANCH_FIRST)
+        hipLaunchKernelGGL(k_batch_branch_select<RULE_BLAND>, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
+                           (const uint8_t *)dmask.p, nmask, pitch, int_tol, (BranchPick *)dout.p);
+    else
+        hipLaunchKernelGGL(k_batch_branch_select<RULE_DANTZIG>, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
+                           (const uint8_t *)dmask.p, nmask, pitch, int_tol, (BranchPick *)dout.p);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipMemcpyAsync(out, dout.p, (size_t)b->count * sizeof(BranchPick), hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *row, const int8_t *dir) {
+    const char *call = "lpg_batch_branch";
+    if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
+    *out = nullptr;
+    // what does not depend on the parent first
+    if (n < 1) return bfail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
+    if (!src || !row || !dir) return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !row ? "row" : "dir");
+    for (int64_t c = 0; c < n; c++)
+        if (dir[c] != -1 && dir[c] != 1)
+            return bfail(p, LPG_ERR_ARG, "%s: dir[%lld] = %d (-1: x <= floor(v), +1: x >= ceil(v))", call, (long long)c,
+                         (int)dir[c]);
+    if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
+    if (p->nobj == 2) return wrong_kind(p, call);
+    for (int64_t c = 0; c < n; c++) {
+        if (src[c] < 0 || src[c] >= p->count)
+            return bfail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c,
+                         (long long)src[c], (long long)(p->count - 1));
+        const int64_t m = lp_m(p, src[c]), ncols = lp_ncols(p, src[c]);
+        if (row[c] < 0 || row[c] >= m)
+            return bfail(p, LPG_ERR_ARG, "%s: row[%lld] = %lld outside the rows 0..%lld of LP %lld", call, (long long)c,
+                         (long long)row[c], (long long)(m - 1), (long long)src[c]);
+        if (m + 2 > LPG_BATCH_MAX_DIM || ncols + 1 > LPG_BATCH_MAX_DIM)
+            return bfail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + 2 = %lld, ncols + 1 = %lld exceed %d", call,
+                         (long long)c, (long long)src[c], (long long)(m + 2), (long long)(ncols + 1), LPG_BATCH_MAX_DIM);
+    }
+    // the child batch: the creation of its layout, with the parent's flags
+    lpg_batch *ch = nullptr;
+    int rc;
+    if (p->ragged) {
+        std::vector<int64_t> ms((size_t)n), ncs((size_t)n);
+        for (int64_t c = 0; c < n; c++) ms[(size_t)c] = lp_m(p, src[c]) + 1, ncs[(size_t)c] = lp_ncols(p, src[c]) + 1;
+        rc = ragged_create(&ch, p->device, n, ms.data(), ncs.data(), 1, p->flags);
+    } else {
+        rc = batch_create(&ch, p->device, n, p->m + 1, p->ncols + 1, p->flags, 1, call);
+    }
+    if (rc) return bfail(p, rc, "%s: the child batch: %s", call, g_berr);
+    auto die = [&](int code) {
+        snprintf(g_berr, sizeof g_berr, "%s", ch->err);
+        snprintf(p->err, sizeof p->err, "%s", ch->err);
+        lpg_batch_destroy(ch);
+        return code;
+    };
+    ch->eps_piv = p->eps_piv;
+    ch->eps_opt = p->eps_opt;
+    if (p->ragged) {
+        for (int64_t c = 0; c < n; c++) {
+            ch->shape[(size_t)c].nact = p->shape[(size_t)src[c]].nact + 1;
+            ch->shape[(size_t)c].art_first = p->shape[(size_t)src[c]].art_first + 1;
+        }
+        if ((rc = push_shapes(ch))) return die(rc);
+    } else {
+        ch->nact = p->nact + 1;
+    }
+    std::vector<BranchJob> jobs((size_t)n);
+    for (int64_t c = 0; c < n; c++) jobs[(size_t)c] = BranchJob{(int32_t)src[c], (int32_t)row[c], (int32_t)dir[c], 0};
+    DevBuf djobs;
+    if (hipMalloc(&djobs.p, jobs.size() * sizeof(BranchJob)) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs) failed", call, (long long)n);
+        return die(LPG_ERR_OOM);
+    }
+    // the parent's stream is idle (every call on it ends with a synchronisation); the copy runs on the child's
+    hipError_t e = hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(BranchJob), hipMemcpyHostToDevice, ch->stream);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)n), block(kBlock);
+        if (p->ragged)
+            hipLaunchKernelGGL(k_batch_branch<true>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch),
+                               (const BranchJob *)djobs.p);
+        else
+            hipLaunchKernelGGL(k_batch_branch<false>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch),
+                               (const BranchJob *)djobs.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    *out = ch;
+    return 0;
+}
 
 }  // namespace
 
@@ -1653,6 +1911,27 @@ int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int6
         }
     }
     return rec;
+}
+
+int lpg_batch_active_columns(const lpg_batch *cb, int64_t lp, int64_t *nact, int64_t *art_first) {
+    lpg_batch *b = const_cast<lpg_batch *>(cb);
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_active_columns: batch is NULL");
+    if (lp < 0 || lp >= b->count)
+        return bfail(b, LPG_ERR_ARG, "lpg_batch_active_columns: LP %lld outside the batch of %lld", (long long)lp,
+                     (long long)b->count);
+    if (nact) *nact = lp_nact(b, lp);
+    if (art_first) *art_first = b->ragged ? b->shape[(size_t)lp].art_first : b->ncols;
+    return 0;
+}
+
+int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
+                            lpg_branch_t *out) {
+    return branch_select(b, mask, nmask, ld_mask, int_tol, rule, out);
+}
+
+int lpg_batch_branch(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *row,
+                     const int8_t *dir) {
+    return branch(child, parent, n, src, row, dir);
 }
 
 }  // extern "C"

@@ -307,13 +307,16 @@ class BatchEngine:
         """A batch of len(shapes) LPs, LP q of shapes[q] = (m, ncols)."""
         return RaggedBatchEngine(shapes, device=device, big_m=big_m, flags=flags, lib=lib)
 
-    def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None, big_m: bool = False):
+    def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None, big_m: bool = False,
+                 _handle=None):
+        """``_handle``: an lpg_batch of this shape that the library already made (branch()); the engine owns it."""
         self.lib = lib if lib is not None else L.load()
-        self._b = ctypes.c_void_p()
-        name = "lpg_batch_create_big_m" if big_m else "lpg_batch_create"
-        rc = getattr(self.lib, name)(ctypes.byref(self._b), device, count, m, ncols, flags)
-        if rc != 0:
-            raise LPGError(f"{name} rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+        self._b = ctypes.c_void_p() if _handle is None else _handle
+        if _handle is None:
+            name = "lpg_batch_create_big_m" if big_m else "lpg_batch_create"
+            rc = getattr(self.lib, name)(ctypes.byref(self._b), device, count, m, ncols, flags)
+            if rc != 0:
+                raise LPGError(f"{name} rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
         self.count, self.m, self.ncols, self.nobj = count, m, ncols, 2 if big_m else 1
 
     def close(self):
@@ -450,6 +453,46 @@ class BatchEngine:
                                                r.ctypes.data_as(L.c_int64_p), n), "lpg_batch_get_log")
         return k[:n], r[:n]
 
+    # -- branching -------------------------------------------------------
+    def active_columns(self, lp: int = 0):
+        """(nact, art_first) of LP lp: its priced columns 1..nact, and a ragged batch's recorded art_first."""
+        nact, af = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.lib.lpg_batch_active_columns(self._b, lp, ctypes.byref(nact), ctypes.byref(af)),
+                    "lpg_batch_active_columns")
+        return int(nact.value), int(af.value)
+
+    def branch_select(self, mask, int_tol: float = 1e-6, rule: int = L.BRANCH_MOST_FRACTIONAL):
+        """The branching row of every LP (include/lpg.h lpg_batch_branch_select). mask: [nmask] (the same for
+        every LP) or [count, nmask], non-zero where tableau column 1 + index is integer-constrained. Returns
+        (row, col, value), one entry per LP; row = col = -1 where every integer column is integral."""
+        mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mk.ndim not in (1, 2) or (mk.ndim == 2 and mk.shape[0] != self.count):
+            raise LPGError(f"branch_select: mask of shape {mk.shape}, want [nmask] or [{self.count}, nmask]")
+        out = (L.Branch * self.count)()
+        self._check(self.lib.lpg_batch_branch_select(self._b, mk.ctypes.data_as(L.c_uint8_p), mk.shape[-1],
+                                                     mk.shape[1] if mk.ndim == 2 else 0, int_tol, rule, out),
+                    "lpg_batch_branch_select")
+        a = np.frombuffer(out, dtype=np.dtype([("row", np.int64), ("col", np.int64), ("value", np.float64)]))
+        return a["row"].copy(), a["col"].copy(), a["value"].copy()
+
+    def branch(self, src, row, dir):
+        """A new batch of len(src) children made on the device (include/lpg.h lpg_batch_branch): child c is LP
+        src[c] plus the bound x <= floor(v) (dir[c] = -1) or x >= ceil(v) (dir[c] = +1) on the variable basic in
+        row[c]; solve_dual() re-optimises it. The engine returned is of this engine's class."""
+        src = np.ascontiguousarray(src, dtype=np.int64)
+        row = np.ascontiguousarray(row, dtype=np.int64)
+        d = np.ascontiguousarray(dir, dtype=np.int8)
+        if src.ndim != 1 or row.shape != src.shape or d.shape != src.shape:
+            raise LPGError(f"branch: src, row, dir of shapes {src.shape}, {row.shape}, {d.shape}, want three [n]")
+        child = ctypes.c_void_p()
+        self._check(self.lib.lpg_batch_branch(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
+                                              row.ctypes.data_as(L.c_int64_p), d.ctypes.data_as(L.c_int8_p)),
+                    "lpg_batch_branch")
+        return self._child(child, src)
+
+    def _child(self, handle, src):
+        return BatchEngine(len(src), self.m + 1, self.ncols + 1, lib=self.lib, _handle=handle)
+
 
 class RaggedBatchEngine(BatchEngine):
     """BatchEngine.ragged(shapes): LPs of different shapes in one batch
@@ -459,9 +502,9 @@ class RaggedBatchEngine(BatchEngine):
     get_log and info are BatchEngine's (info reports the largest m, ncols, ld and
     lds_bytes). The packing to and from the C ABI's flat arrays happens here."""
 
-    def __init__(self, shapes, device: int = 0, big_m: bool = False, flags: int = 0, lib=None):
+    def __init__(self, shapes, device: int = 0, big_m: bool = False, flags: int = 0, lib=None, _handle=None):
         self.lib = lib if lib is not None else L.load()
-        self._b = ctypes.c_void_p()
+        self._b = ctypes.c_void_p() if _handle is None else _handle
         try:
             self.shapes = [(int(m), int(nc)) for m, nc in shapes]
         except (TypeError, ValueError) as e:
@@ -469,11 +512,15 @@ class RaggedBatchEngine(BatchEngine):
         self.count, self.nobj = len(self.shapes), 2 if big_m else 1
         ms = np.array([m for m, _ in self.shapes], dtype=np.int64)
         ncs = np.array([nc for _, nc in self.shapes], dtype=np.int64)
-        rc = self.lib.lpg_batch_create_ragged(ctypes.byref(self._b), device, self.count, ms.ctypes.data_as(L.c_int64_p),
-                                              ncs.ctypes.data_as(L.c_int64_p), self.nobj, flags)
-        if rc != 0:
-            raise LPGError(f"lpg_batch_create_ragged rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+        if _handle is None:
+            rc = self.lib.lpg_batch_create_ragged(ctypes.byref(self._b), device, self.count, ms.ctypes.data_as(L.c_int64_p),
+                                                  ncs.ctypes.data_as(L.c_int64_p), self.nobj, flags)
+            if rc != 0:
+                raise LPGError(f"lpg_batch_create_ragged rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
         self.m, self.ncols = int(ms.max()), int(ncs.max())
+
+    def _child(self, handle, src):
+        return RaggedBatchEngine([(self.shapes[q][0] + 1, self.shapes[q][1] + 1) for q in src], lib=self.lib, _handle=handle)
 
     def shape(self, lp: int) -> L.BatchShape:
         s = L.BatchShape()

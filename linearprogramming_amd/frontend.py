@@ -20,6 +20,9 @@ the reference binary's transcripts). Stages, each citing what it restates:
 * ``solve``        the device solve and readout the bridge performs
                    (integration/lpg_bridge.c LPGSolveSMatrix): rows without a
                    true unit column get artificials (two-phase or Big-M)
+* ``solve_ilp``    integer LPs (the reference's wish-list, README): branch and
+                   bound whose node LPs are a batch, a level per
+                   BatchEngine.branch + solve_dual ("Branching")
 
 The variable table mirrors hashTable.c (PutVarItem replaces an existing key in
 place; GetVarItems walks buckets in hash order, VarHash hashTable.c:148-167).
@@ -849,6 +852,126 @@ def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) ->
 def solve_text(text: str, method: str = "two_phase", rule=None, device: int = 0) -> LPSolution:
     """LP text (the reference's input format) -> the optimum on the device."""
     return solve(build_smatrix(text, dual=method == "dual"), method=method, rule=rule, device=device)
+
+
+@dataclass
+class ILPSolution(LPSolution):
+    """LPSolution of the best integer point found (status OPTIMAL, or NODE_LIMIT with the incumbent so far;
+    INFEASIBLE when the tree holds none), `pivots` summed over every node LP."""
+    nodes: int = 0               # node LPs solved: the root and every child made
+    depth: int = 0               # levels of the tree that held an OPTIMAL node, the root's included
+
+
+def text_variables(text: str) -> list:
+    """The variables the text itself names (objective, then constraints, in order of appearance), from
+    parse(text) before LPTrans moves sign constraints away and LPStandardize adds slacks."""
+    m = parse(text)
+    seen = []
+    for t in m.objective + [t for st in m.rows for t in st.left + st.right]:
+        if t.var and t.var not in seen:
+            seen.append(t.var)
+    return seen
+
+
+def integer_mask(sm: SMatrix, integer) -> np.ndarray:
+    """The uint8 mask over standard-form columns 1..len(sm.names) of the user's integer variables: a variable's
+    own column (the inverted one of an x <= 0 variable), or both columns of a free variable x = former - latter
+    (branching on whichever of the two is basic and fractional is complete: every integer x has a
+    representation with one of them zero)."""
+    mask = np.zeros(len(sm.names), dtype=np.uint8)
+    for name in integer:
+        it = sm.vars.get(name) if sm.vars is not None else None
+        if it is None:
+            raise FrontendError(f"solve_ilp: {name!r} is not a variable of the model")
+        for col in ([it.former, it.latter] if (it.relation == 0 and it.former) else [name]):
+            if col not in sm.names:
+                raise FrontendError(f"solve_ilp: {name!r} has no column in the standard form")
+            mask[sm.names.index(col)] = 1
+    return mask
+
+
+def solve_ilp(sm: SMatrix, integer, *, int_tol: float = 1e-6, node_limit: int = 100000, rule=None,
+              device: int = 0) -> ILPSolution:
+    """Branch and bound on the device: the variables named in ``integer`` must be integers.
+
+    Level-synchronous and breadth-first, fixed so that a CPU restatement follows it node for node
+    (tests/branch_cases.py reference_walk). The root is solved as solve() solves it (the primal simplex, or
+    two-phase where rows lack a basic column) in a batch of one. Then, per level: branch_select on the level's
+    batch (``rule``: BRANCH_MOST_FRACTIONAL by default); of the nodes with no fractional integer variable the
+    best (larger max-form objective, then lower index) replaces the incumbent if strictly better; a remaining
+    node whose objective is <= the incumbent's is dropped; every survivor gets two children, down before up,
+    parents ascending, all made by one branch() and re-optimised by one solve_dual(); INFEASIBLE children are
+    dropped, OPTIMAL ones are the next level, any other status ends the call with it. The walk stops when a
+    level is empty or more than ``node_limit`` node LPs have been solved (status NODE_LIMIT). The tableaus
+    never leave the device: the host sees one status, objective and branching row per node, and the rows and
+    basis of an incumbent."""
+    from . import _lib as L
+    from .engine import BatchEngine
+    if rule is None:
+        rule = L.BRANCH_MOST_FRACTIONAL
+    mask = integer_mask(sm, integer)
+    rows, basis, cost, nc0, nlack = engine_arrays(sm)
+    m, nc = rows.shape
+    T = np.zeros((1, m + 1, nc), dtype=np.float64)
+    T[0, :m] = rows
+    batch = BatchEngine(1, m, nc, device=device)
+    try:
+        batch.load(T, np.asarray(basis, dtype=np.int64)[None])
+        if nlack:
+            res, used = batch.solve_two_phase(nc0, cost), "two_phase"
+        else:
+            batch.set_objective(cost)
+            res, used = batch.solve(), "primal"
+        sol = ILPSolution(res[0].status_name, int(res[0].pivots), method=used, nodes=1, depth=1)
+        if res[0].status != L.OPTIMAL:
+            return sol
+        alive, objective = [0], [res[0].objective]           # the level: LPs of `batch`, their objectives
+        best = None                                          # (objective, x_B, basis, ncols) of the incumbent
+        while alive:
+            if sol.nodes > node_limit:
+                sol.status = "NODE_LIMIT"
+                break
+            pick, _, _ = batch.branch_select(mask, int_tol, rule)
+            cand = None
+            for q in alive:
+                if pick[q] < 0 and (cand is None or objective[q] > objective[cand]):
+                    cand = q
+            if cand is not None and (best is None or objective[cand] > best[0]):
+                tab = batch.get_rows(cand, 1)[0]
+                best = (objective[cand], tab[:-1, 0].copy(), batch.get_basis(cand, 1)[0], tab.shape[1])
+            parents = [q for q in alive if pick[q] >= 0 and not (best is not None and objective[q] <= best[0])]
+            if not parents:
+                break
+            src = np.repeat(np.asarray(parents, dtype=np.int64), 2)
+            child = batch.branch(src, pick[src], np.tile(np.array([-1, 1], dtype=np.int8), len(parents)))
+            batch.close()
+            batch = child
+            res = batch.solve_dual()
+            sol.nodes += len(res)
+            sol.pivots += sum(int(r.pivots) for r in res)
+            other = [r for r in res if r.status not in (L.OPTIMAL, L.INFEASIBLE)]
+            if other:
+                sol.status = other[0].status_name
+                return sol
+            alive = [c for c, r in enumerate(res) if r.status == L.OPTIMAL]
+            objective = [r.objective for r in res]
+            if alive:
+                sol.depth += 1
+    finally:
+        batch.close()
+    if best is None:
+        if sol.status == "OPTIMAL":
+            sol.status = "INFEASIBLE"
+        return sol
+    return _readout(sm, sol, best[0], best[1], best[2], best[3])
+
+
+def solve_ilp_text(text: str, integer=None, *, int_tol: float = 1e-6, node_limit: int = 100000, rule=None,
+                   device: int = 0) -> ILPSolution:
+    """LP text -> the integer optimum; ``integer=None``: every variable the text itself names."""
+    if integer is None:
+        integer = text_variables(text)
+    return solve_ilp(build_smatrix(text), integer, int_tol=int_tol, node_limit=node_limit, rule=rule, device=device)
 
 
 def main(argv=None) -> int:

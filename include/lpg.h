@@ -560,6 +560,71 @@ int  lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, i
 int  lpg_batch_branch(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *row,
                       const int8_t *dir);
 
+/* ---- cuts: a round of Gomory mixed-integer cuts on the LPs of a batch ----
+ *
+ * The other way from a fractional optimum towards an integer one: instead of
+ * two children with one bound row each, one child with k cut rows, each of
+ * which the fractional vertex violates and no integer point does. The shape of
+ * the work is lpg_batch_branch's: the child is the parent's tableau in its
+ * current basis plus rows with basic slacks and negative right-hand sides, dual
+ * feasible wherever the parent was LPG_OPTIMAL, so lpg_batch_solve_dual(child)
+ * re-optimises it, and no tableau crosses the host. Both calls work on batches
+ * of one shape and on ragged ones and refuse a Big-M batch (LPG_ERR_STATE).
+ *
+ * The cut (Gomory mixed-integer, GMI) of LP s from row r, whose basic column is
+ * integer-constrained; 1..nact the active columns, B the basis, v = T[r][0]:
+ *     frac(x) = x - floor(x), and 0.0 where that difference is >= 1.0 (a tiny
+ *               negative x rounds to exactly 1.0 otherwise)
+ *     f0  = frac(v)
+ *     rho = f0 / (1.0 - f0)                         one IEEE division per cut
+ * and for column j in 1..nact with a = T[r][j]
+ *     j basic in any row of the LP (by membership in B, not by value):
+ *                                  g = 0.0
+ *     j integer-constrained:       f = frac(a), g = f <= f0 ? f : rho * (1.0 - f)
+ *     otherwise (continuous):      g = a >= 0.0 ? a : rho * (-a)
+ * and g = 0.0 for the columns behind nact (the inert artificials of a two-phase
+ * parent). The new row holds -g_j in column j, -f0 in column 0, 1.0 in its own
+ * new slack column and 0.0 in the other new slack columns. It is valid for any
+ * real coefficients given only the mask: slacks, branch slacks and the slacks
+ * of earlier cuts count as continuous. Only floor, subtraction, one division,
+ * multiplication, negation and comparisons are used, each a single rounding
+ * (nothing is contracted into an fma, the division is the IEEE one), so a host
+ * restatement reproduces every bit (tests/cut_cases.py). */
+#define LPG_BATCH_MAX_CUTS 1024   /* cuts per child: their (f0, rho) records and the basic-column byte map share the LDS */
+/* The cut rows of every LP q (k_batch_cut_select, one workgroup per LP): the
+ * candidates are lpg_batch_branch_select's (basic column masked, min(f, 1 - f)
+ * > int_tol, the mask addressed as there); ncut[q] = min(max_cuts, candidates)
+ * and rows[q * max_cuts ..] lists that many in LPG_BRANCH_MOST_FRACTIONAL
+ * order, largest distance first, ties to the smallest column; unused slots are
+ * -1. LPG_ERR_ARG before any device work: NULL arguments, max_cuts outside
+ * 1..LPG_BATCH_MAX_CUTS, int_tol not in [0, 0.5) (these three before the batch
+ * is looked at), nmask outside 1..ncols-1, 0 < ld_mask < nmask. */
+int  lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask,
+                          double int_tol, int64_t max_cuts,
+                          int64_t *ncut /* count */, int64_t *rows /* count * max_cuts */);
+/* *child = a new batch of n LPs: child c is LP src[c] of `parent` plus one cut
+ * per row in rows[first[c] .. first[c+1]) (first has n + 1 entries, first[0] =
+ * 0), k_c = first[c+1] - first[c] of them: 1 <= k_c <= LPG_BATCH_MAX_CUTS, the
+ * rows distinct and inside 0..m_src-1. The mask is the parent's, LP src[c] at
+ * mask + src[c] * ld_mask (ld_mask == 0: one mask for every LP). The layout
+ * follows lpg_batch_branch: columns 0..nact keep their place, the new slacks
+ * are columns nact+1 .. nact+k, what lay behind nact moves right by k, as do
+ * basis entries > nact; the new rows are m .. m+k-1 in the order of `rows`,
+ * the basis of new row t is nact+1+t, the objective row becomes row m+k. The
+ * child's active columns are 1..nact+k (a ragged parent's recorded art_first
+ * grows by k as well); it inherits tolerances and flags; its LPs are fresh. The
+ * child is ragged if the parent is ragged or the k_c differ, else of one shape
+ * (m + k, ncols + k). The parent is unchanged. Every argument is checked before
+ * any device work, with a message that names the call and the first offending
+ * index; first the checks that need no parent: n < 1, NULL arrays, first[0] !=
+ * 0, a first[c+1] <= first[c]; then a src outside the parent, a k_c over the
+ * cap, a row out of range or listed twice, a child dimension over
+ * LPG_BATCH_MAX_DIM, the mask's nmask / ld_mask as above (all LPG_ERR_ARG); a
+ * Big-M parent (LPG_ERR_STATE). On any error *child is NULL. */
+int  lpg_batch_cut(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src,
+                   const int64_t *first /* n + 1 offsets into rows */, const int64_t *rows,
+                   const uint8_t *mask, int64_t nmask, int64_t ld_mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ DEFER_MAX = 128
 BATCH_TIER_LDS, BATCH_TIER_GLOBAL = 0, 1
 BATCH_MAX_DIM = 8192
 BRANCH_MOST_FRACTIONAL, BRANCH_FIRST = 0, 1
+BATCH_MAX_CUTS = 1024
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -165,6 +166,10 @@ PROTOTYPES = [
                                                ctypes.c_int, ctypes.POINTER(Branch)]),
     ("lpg_batch_branch", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64, c_int64_p,
                                         c_int64_p, c_int8_p]),
+    ("lpg_batch_cut_select", ctypes.c_int, [ctypes.c_void_p, c_uint8_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                            ctypes.c_int64, c_int64_p, c_int64_p]),
+    ("lpg_batch_cut", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p,
+                                     c_int64_p, c_uint8_p, ctypes.c_int64, ctypes.c_int64]),
 ]
 
 

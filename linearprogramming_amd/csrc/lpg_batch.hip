@@ -46,6 +46,11 @@
 // k_batch_branch_select picks every LP's branching row over its basis;
 // k_batch_branch makes the batch of the children, each its parent's tableau
 // plus one bound row and one slack column, by a copy in device memory.
+//
+// Cuts (lpg_batch_cut_select, lpg_batch_cut): a round of Gomory mixed-integer
+// cuts on a batch. k_batch_cut_select lists every LP's most fractional rows;
+// k_batch_cut makes the batch of the children, each its parent's tableau plus
+// one cut row and one slack column per listed row, by the same kind of copy.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -863,6 +868,152 @@ __global__ __launch_bounds__(kBlock) void k_batch_branch(BatchGeo p, BatchGeo c,
     for (int64_t i = tid; i <= m; i += kBlock) cB[i] = i == m ? nact + 1 : (pB[i] > nact ? pB[i] + 1 : pB[i]);
 }
 
+// ------------------------------------------------------------------------
+// cuts (include/lpg.h, "cuts"): a round of Gomory mixed-integer cuts on the
+// tableaus where the solve calls left them. Every operation of the cut is one
+// rounding (the file is built with -ffp-contract=off; the product and the
+// quotient are spelled __dmul_rn / __ddiv_rn), so tests/cut_cases.py
+// reproduces every bit.
+// ------------------------------------------------------------------------
+
+// x - floor(x), and 0 where that difference rounds to 1 (a tiny negative x)
+__device__ __forceinline__ double cut_frac(double x) {
+    const double f = x - floor(x);
+    return f >= 1.0 ? 0.0 : f;
+}
+
+// The cut rows of LP blockIdx.x: branch_select's candidates, the `max_cuts`
+// best in LPG_BRANCH_MOST_FRACTIONAL order, by repeated extraction: round t
+// takes the block argmin over the candidates that come strictly behind pick
+// t - 1 in that order (a total one: the basic columns of an LP differ).
+__global__ __launch_bounds__(kBlock) void k_batch_cut_select(BatchGeo g, const uint8_t *mask, int64_t nmask, int64_t ld_mask,
+                                                             double int_tol, int64_t max_cuts, int64_t *ncut, int64_t *rows) {
+    const int64_t q = blockIdx.x;
+    const LpGeo s = g.shape ? lp_geo<true>(g, q, 1, 0) : lp_geo<false>(g, q, 1, 0);
+    const double *T = g.T + s.t_off;
+    const int64_t *gB = g.basis + s.b_off;
+    const uint8_t *mk = mask + q * ld_mask;
+    int64_t *out = rows + q * max_cuts;
+    double last_v = 0.0;
+    int64_t last_j = -1, t = 0;
+    for (; t < max_cuts; t++) {
+        PricePart pb{0.0, -1, 0, 0};
+        for (int64_t i = threadIdx.x; i < s.m; i += kBlock) {
+            const int64_t bj = gB[i];
+            const bool integer = (bj >= 1) & (bj <= nmask) && mk[bj - 1] != 0;
+            const double v = T[i * s.ld];
+            const double f = v - floor(v), f1 = 1.0 - f;
+            const double dist = f < f1 ? f : f1;
+            const bool behind = (t == 0) | (-dist > last_v) | ((-dist == last_v) & (bj > last_j));
+            PricePart c{-dist, (integer & (dist > int_tol) & behind) ? bj : -1, 0, (int32_t)i};
+            pp_take(pb, c, pp_better<RULE_DANTZIG>(c, pb));
+        }
+        pb = block_argmin_pp<RULE_DANTZIG>(pb);
+        if (pb.j < 0) break;                                   // uniform: every thread holds the block's pick
+        last_v = pb.v;
+        last_j = pb.j;
+        if (threadIdx.x == 0) out[t] = pb.pad;
+    }
+    if (threadIdx.x == 0) ncut[q] = t;
+    for (int64_t u = t + threadIdx.x; u < max_cuts; u += kBlock) out[u] = -1;
+}
+
+struct CutJob {               // child c of lpg_batch_cut: validated on the host
+    int32_t src, first, k, pad;   // its source LP, its rows at rows[first .. first + k)
+};
+
+// entry j of a cut row from the source row's entry a in column j of the
+// parent (include/lpg.h, "cuts"): -f0 in column 0, else -g_j
+__device__ __forceinline__ double cut_entry(double a, int64_t j, int64_t nact, const uint8_t *basic, const uint8_t *mk,
+                                            int64_t nmask, double f0, double rho) {
+    if (j == 0) return -f0;
+    double g;
+    if (j > nact || basic[j]) g = 0.0;
+    else if (j <= nmask && mk[j - 1]) {
+        const double f = cut_frac(a);
+        g = f <= f0 ? f : __dmul_rn(rho, 1.0 - f);
+    } else g = a >= 0.0 ? a : __dmul_rn(rho, -a);
+    return -g;
+}
+
+// Child blockIdx.x of `c` from LP job.src of `p` (RG: the parent is ragged,
+// and then the child is; a parent of one shape has a ragged child where the
+// cut counts differ). k_batch_branch's streaming copy with k new rows and k
+// new columns: the prologue marks the source's basic columns in an LDS byte
+// map and computes (f0, rho) of every cut; then columns 0..nact keep their
+// place and move as 16-byte pairs, and the rest of a row (the k slack columns
+// nact + 1.., behind them the parent's columns nact + 1.. moved right by k,
+// which an odd k takes off the 16-byte grid) moves as doubles. Child row i is
+// the parent's row i (i < m), the cut from row sRow[i - m] (m <= i < m + k) or
+// the parent's objective row (i = m + k).
+template <bool RG>
+__global__ __launch_bounds__(kBlock) void k_batch_cut(BatchGeo p, BatchGeo c, const CutJob *jobs, const int32_t *rows,
+                                                      const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
+    __shared__ double sF0[LPG_BATCH_MAX_CUTS], sRho[LPG_BATCH_MAX_CUTS];
+    __shared__ int32_t sRow[LPG_BATCH_MAX_CUTS];
+    __shared__ uint32_t sBasicWords[LPG_BATCH_MAX_DIM / 4];
+    uint8_t *sBasic = (uint8_t *)sBasicWords;
+
+    const CutJob job = jobs[blockIdx.x];
+    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0);
+    const LpGeo cs = (RG || c.shape) ? lp_geo<true>(c, blockIdx.x, 1, 0) : lp_geo<false>(c, blockIdx.x, 1, 0);
+    const double *pT = p.T + ps.t_off;
+    double *cT = c.T + cs.t_off;
+    const int64_t *pB = p.basis + ps.b_off;
+    int64_t *cB = c.basis + cs.b_off;
+    const uint8_t *mk = mask + (int64_t)job.src * ld_mask;
+    const int64_t m = ps.m, nc = ps.ncols, nact = ps.nact, pld = ps.ld, cld = cs.ld, k = job.k;
+    const int tid = threadIdx.x;
+
+    for (int64_t w = tid; w < (nc + 3) >> 2; w += kBlock) sBasicWords[w] = 0;
+    for (int64_t t = tid; t < k; t += kBlock) {
+        const int32_t r = rows[job.first + t];
+        const double f0 = cut_frac(pT[r * pld]);
+        sRow[t] = r;
+        sF0[t] = f0;
+        sRho[t] = __ddiv_rn(f0, 1.0 - f0);
+    }
+    __syncthreads();
+    for (int64_t i = tid; i < m; i += kBlock) {
+        const int64_t bj = pB[i];
+        if (bj >= 0 && bj < nc) sBasic[bj] = 1;
+    }
+    __syncthreads();
+
+    const int npair = (int)((nact + 1) >> 1), w0 = 2 * npair;      // columns [0, w0) as pairs
+    int txs = 0;
+    while ((1 << txs) < npair && txs < 8) txs++;
+    const int tx = 1 << txs, ty = kBlock >> txs, j0 = tid & (tx - 1), i0 = tid >> txs;
+    for (int64_t i = i0; i < m + k + 1; i += ty) {
+        const bool cut = (i >= m) & (i < m + k);
+        const int64_t t = cut ? i - m : 0;
+        const int64_t si = i < m ? i : (cut ? (int64_t)sRow[t] : m);
+        const double f0 = sF0[t], rho = sRho[t];               // read only where `cut`
+        const double *prow = pT + si * pld;
+        double *crow = cT + i * cld;
+        for (int j = 2 * j0; j < w0; j += 2 * tx) {
+            d2 x = *(const d2 *)(prow + j);
+            if (cut) {
+                x.x = cut_entry(x.x, j, nact, sBasic, mk, nmask, f0, rho);
+                x.y = cut_entry(x.y, j + 1, nact, sBasic, mk, nmask, f0, rho);
+            }
+            *(d2 *)(crow + j) = x;
+        }
+        // child columns [w0, nc + k): at most one unshifted column, the slacks, the shifted columns
+        for (int64_t j = w0 + j0; j < nc + k; j += tx) {
+            double y;
+            if (j > nact && j <= nact + k) y = (cut && j == nact + 1 + t) ? 1.0 : 0.0;
+            else {
+                const int64_t pj = j <= nact ? j : j - k;
+                y = prow[pj];
+                if (cut) y = cut_entry(y, pj, nact, sBasic, mk, nmask, f0, rho);
+            }
+            crow[j] = y;
+        }
+    }
+    for (int64_t i = tid; i < m + k; i += kBlock) cB[i] = i >= m ? nact + 1 + (i - m) : (pB[i] > nact ? pB[i] + k : pB[i]);
+}
+
 }  // namespace lpg
 
 // ---------------------------------------------------------------------------
@@ -1477,18 +1628,24 @@ struct DevBuf {
     }
 };
 
-int branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
-                  lpg_branch_t *out) {
-    const char *call = "lpg_batch_branch_select";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
-    if (!mask || !out) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
-    if (b->nobj == 2) return wrong_kind(b, call);
+// the mask checks of the calls that take one, once the batch is known
+int mask_ok(lpg_batch *b, const char *call, int64_t nmask, int64_t ld_mask) {
     if (nmask < 1 || nmask > b->ncols - 1)
         return bfail(b, LPG_ERR_ARG, "%s: nmask %lld outside 1..%lld (the columns of the %s)", call, (long long)nmask,
                      (long long)(b->ncols - 1), b->ragged ? "widest LP" : "batch");
     if (ld_mask != 0 && ld_mask < nmask)
         return bfail(b, LPG_ERR_ARG, "%s: ld_mask %lld < nmask %lld (0: one mask for every LP)", call, (long long)ld_mask,
                      (long long)nmask);
+    return 0;
+}
+
+int branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
+                  lpg_branch_t *out) {
+    const char *call = "lpg_batch_branch_select";
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (!mask || !out) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
+    if (b->nobj == 2) return wrong_kind(b, call);
+    if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
     if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
     if (rule != LPG_BRANCH_MOST_FRACTIONAL && rule != LPG_BRANCH_FIRST) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
     BHIPCHK(b, hipSetDevice(b->device));
@@ -1586,6 +1743,160 @@ int branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const i
         else
             hipLaunchKernelGGL(k_batch_branch<false>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch),
                                (const BranchJob *)djobs.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
+        return die(LPG_ERR_DEVICE);
+    }
+    *out = ch;
+    return 0;
+}
+
+int cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int64_t max_cuts,
+               int64_t *ncut, int64_t *rows) {
+    const char *call = "lpg_batch_cut_select";
+    // what does not depend on the batch first
+    if (!mask || !ncut || !rows)
+        return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : !ncut ? "ncut" : "rows");
+    if (max_cuts < 1 || max_cuts > LPG_BATCH_MAX_CUTS)
+        return bfail(b, LPG_ERR_ARG, "%s: max_cuts = %lld outside 1..%d", call, (long long)max_cuts, LPG_BATCH_MAX_CUTS);
+    if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (b->nobj == 2) return wrong_kind(b, call);
+    if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
+    BHIPCHK(b, hipSetDevice(b->device));
+    const int64_t nrows = ld_mask ? b->count : 1;
+    const size_t nbytes = (size_t)b->count * sizeof(int64_t), rbytes = nbytes * (size_t)max_cuts;
+    DevBuf dmask, dncut, drows;
+    if (hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess || hipMalloc(&dncut.p, nbytes) != hipSuccess ||
+        hipMalloc(&drows.p, rbytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and rows of %lld LPs) failed", call, (long long)b->count);
+    }
+    BHIPCHK(b, hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask,
+                                (size_t)nrows, hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_cut_select, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
+                       (const uint8_t *)dmask.p, nmask, ld_mask ? nmask : (int64_t)0, int_tol, max_cuts, (int64_t *)dncut.p,
+                       (int64_t *)drows.p);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipMemcpyAsync(ncut, dncut.p, nbytes, hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipMemcpyAsync(rows, drows.p, rbytes, hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *first, const int64_t *rows,
+        const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
+    const char *call = "lpg_batch_cut";
+    if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
+    *out = nullptr;
+    // what does not depend on the parent first
+    if (n < 1) return bfail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
+    if (!src || !first || !rows || !mask)
+        return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !first ? "first" : !rows ? "rows" : "mask");
+    if (first[0] != 0) return bfail(p, LPG_ERR_ARG, "%s: first[0] = %lld (the offsets start at 0)", call, (long long)first[0]);
+    for (int64_t c = 0; c < n; c++)
+        if (first[c + 1] <= first[c])
+            return bfail(p, LPG_ERR_ARG, "%s: first[%lld] = %lld is not above first[%lld] = %lld (every child has at least "
+                                         "one cut)", call, (long long)(c + 1), (long long)first[c + 1], (long long)c,
+                         (long long)first[c]);
+    if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
+    if (p->nobj == 2) return wrong_kind(p, call);
+    if (int rc = mask_ok(p, call, nmask, ld_mask)) return rc;
+    bool same_k = true;
+    std::vector<char> seen;
+    for (int64_t c = 0; c < n; c++) {
+        const int64_t k = first[c + 1] - first[c];
+        if (src[c] < 0 || src[c] >= p->count)
+            return bfail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c,
+                         (long long)src[c], (long long)(p->count - 1));
+        if (k > LPG_BATCH_MAX_CUTS)
+            return bfail(p, LPG_ERR_ARG, "%s: child %lld has %lld cuts, more than LPG_BATCH_MAX_CUTS = %d", call, (long long)c,
+                         (long long)k, LPG_BATCH_MAX_CUTS);
+        const int64_t m = lp_m(p, src[c]), ncols = lp_ncols(p, src[c]);
+        seen.assign((size_t)m, 0);
+        for (int64_t t = first[c]; t < first[c + 1]; t++) {
+            if (rows[t] < 0 || rows[t] >= m)
+                return bfail(p, LPG_ERR_ARG, "%s: rows[%lld] = %lld (child %lld) outside the rows 0..%lld of LP %lld", call,
+                             (long long)t, (long long)rows[t], (long long)c, (long long)(m - 1), (long long)src[c]);
+            if (seen[(size_t)rows[t]])
+                return bfail(p, LPG_ERR_ARG, "%s: rows[%lld] = %lld appears twice in child %lld", call, (long long)t,
+                             (long long)rows[t], (long long)c);
+            seen[(size_t)rows[t]] = 1;
+        }
+        if (m + k + 1 > LPG_BATCH_MAX_DIM || ncols + k > LPG_BATCH_MAX_DIM)
+            return bfail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + %lld + 1 = %lld, ncols + %lld = %lld exceed %d", call,
+                         (long long)c, (long long)src[c], (long long)k, (long long)(m + k + 1), (long long)k,
+                         (long long)(ncols + k), LPG_BATCH_MAX_DIM);
+        same_k &= k == first[1];
+    }
+    // the child batch: the creation of its layout, with the parent's flags
+    const bool ragged = p->ragged || !same_k;
+    lpg_batch *ch = nullptr;
+    int rc;
+    if (ragged) {
+        std::vector<int64_t> ms((size_t)n), ncs((size_t)n);
+        for (int64_t c = 0; c < n; c++) {
+            const int64_t k = first[c + 1] - first[c];
+            ms[(size_t)c] = lp_m(p, src[c]) + k, ncs[(size_t)c] = lp_ncols(p, src[c]) + k;
+        }
+        rc = ragged_create(&ch, p->device, n, ms.data(), ncs.data(), 1, p->flags);
+    } else {
+        rc = batch_create(&ch, p->device, n, p->m + first[1], p->ncols + first[1], p->flags, 1, call);
+    }
+    if (rc) return bfail(p, rc, "%s: the child batch: %s", call, g_berr);
+    auto die = [&](int code) {
+        snprintf(g_berr, sizeof g_berr, "%s", ch->err);
+        snprintf(p->err, sizeof p->err, "%s", ch->err);
+        lpg_batch_destroy(ch);
+        return code;
+    };
+    ch->eps_piv = p->eps_piv;
+    ch->eps_opt = p->eps_opt;
+    if (ragged) {
+        // a parent of one shape records no art_first (lpg_batch_active_columns: ncols), and neither does its child
+        for (int64_t c = 0; c < n; c++) {
+            const int64_t k = first[c + 1] - first[c];
+            ch->shape[(size_t)c].nact = (int32_t)(lp_nact(p, src[c]) + k);
+            if (p->ragged) ch->shape[(size_t)c].art_first = p->shape[(size_t)src[c]].art_first + (int32_t)k;
+        }
+        if ((rc = push_shapes(ch))) return die(rc);
+    } else {
+        ch->nact = p->nact + first[1];
+    }
+    std::vector<CutJob> jobs((size_t)n);
+    std::vector<int32_t> rows32((size_t)first[n]);
+    for (int64_t c = 0; c < n; c++)
+        jobs[(size_t)c] = CutJob{(int32_t)src[c], (int32_t)first[c], (int32_t)(first[c + 1] - first[c]), 0};
+    for (int64_t t = 0; t < first[n]; t++) rows32[(size_t)t] = (int32_t)rows[t];
+    const int64_t nrows = ld_mask ? p->count : 1;
+    DevBuf djobs, drows, dmask;
+    if (hipMalloc(&djobs.p, jobs.size() * sizeof(CutJob)) != hipSuccess ||
+        hipMalloc(&drows.p, rows32.size() * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, %lld rows, masks) failed", call, (long long)n, (long long)first[n]);
+        return die(LPG_ERR_OOM);
+    }
+    // the parent's stream is idle (every call on it ends with a synchronisation); the copy runs on the child's
+    hipError_t e = hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(CutJob), hipMemcpyHostToDevice, ch->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(drows.p, rows32.data(), rows32.size() * sizeof(int32_t), hipMemcpyHostToDevice, ch->stream);
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask, (size_t)nrows,
+                             hipMemcpyHostToDevice, ch->stream);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)n), block(kBlock);
+        const int64_t pitch = ld_mask ? nmask : 0;
+        if (p->ragged)
+            hipLaunchKernelGGL(k_batch_cut<true>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const CutJob *)djobs.p,
+                               (const int32_t *)drows.p, (const uint8_t *)dmask.p, nmask, pitch);
+        else
+            hipLaunchKernelGGL(k_batch_cut<false>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const CutJob *)djobs.p,
+                               (const int32_t *)drows.p, (const uint8_t *)dmask.p, nmask, pitch);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
@@ -1932,6 +2243,16 @@ int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, in
 int lpg_batch_branch(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *row,
                      const int8_t *dir) {
     return branch(child, parent, n, src, row, dir);
+}
+
+int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int64_t max_cuts,
+                         int64_t *ncut, int64_t *rows) {
+    return cut_select(b, mask, nmask, ld_mask, int_tol, max_cuts, ncut, rows);
+}
+
+int lpg_batch_cut(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *first,
+                  const int64_t *rows, const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
+    return cut(child, parent, n, src, first, rows, mask, nmask, ld_mask);
 }
 
 }  // extern "C"

@@ -493,6 +493,54 @@ class BatchEngine:
     def _child(self, handle, src):
         return BatchEngine(len(src), self.m + 1, self.ncols + 1, lib=self.lib, _handle=handle)
 
+    # -- cuts ------------------------------------------------------------
+    def _mask(self, mask, what):
+        """mask: [nmask] or [count, nmask] -> the uint8 array, its pointer, nmask and pitch (0: one for every LP)."""
+        mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mk.ndim not in (1, 2) or (mk.ndim == 2 and mk.shape[0] != self.count):
+            raise LPGError(f"{what}: mask of shape {mk.shape}, want [nmask] or [{self.count}, nmask]")
+        return mk, mk.ctypes.data_as(L.c_uint8_p), mk.shape[-1], mk.shape[1] if mk.ndim == 2 else 0
+
+    def cut_select(self, mask, int_tol: float = 1e-6, max_cuts: int = 8) -> list:
+        """The cut rows of every LP (include/lpg.h lpg_batch_cut_select): branch_select's candidates, at most
+        max_cuts of them, most fractional first, ties to the smallest column. mask as branch_select's. Returns one
+        int64 array of rows per LP (empty where every integer column is integral)."""
+        mk, mp, nmask, ld = self._mask(mask, "cut_select")
+        ncut = np.zeros(self.count, dtype=np.int64)
+        rows = np.zeros((self.count, max(int(max_cuts), 1)), dtype=np.int64)
+        self._check(self.lib.lpg_batch_cut_select(self._b, mp, nmask, ld, int_tol, max_cuts, ncut.ctypes.data_as(L.c_int64_p),
+                                                  rows.ctypes.data_as(L.c_int64_p)), "lpg_batch_cut_select")
+        return [rows[q, :ncut[q]].copy() for q in range(self.count)]
+
+    def cut(self, src, rows_per_child, mask):
+        """A new batch of len(src) children made on the device (include/lpg.h lpg_batch_cut): child c is LP src[c]
+        plus one Gomory mixed-integer cut per row in rows_per_child[c] (at least one; distinct rows); mask as
+        cut_select's, indexed by this batch's LPs; solve_dual() re-optimises the child. Returns a BatchEngine, or a
+        RaggedBatchEngine where this batch is ragged or the children's cut counts differ, as the library made it."""
+        src = np.ascontiguousarray(src, dtype=np.int64)
+        per = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows_per_child]
+        if src.ndim != 1 or len(per) != src.shape[0]:
+            raise LPGError(f"cut: src of shape {src.shape} and {len(per)} row lists, want [n] and n lists")
+        first = np.zeros(len(per) + 1, dtype=np.int64)
+        first[1:] = np.cumsum([len(r) for r in per])
+        rows = np.ascontiguousarray(np.concatenate(per + [np.zeros(0, dtype=np.int64)]))
+        if rows.size == 0:
+            rows = np.zeros(1, dtype=np.int64)           # a pointer to pass; the library refuses the empty interval
+        mk, mp, nmask, ld = self._mask(mask, "cut")
+        child = ctypes.c_void_p()
+        self._check(self.lib.lpg_batch_cut(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
+                                           first.ctypes.data_as(L.c_int64_p), rows.ctypes.data_as(L.c_int64_p), mp, nmask, ld),
+                    "lpg_batch_cut")
+        info = L.BatchInfo()
+        self.lib.lpg_batch_info(child, ctypes.byref(info))
+        shapes = [(self._shape_of(q)[0] + len(r), self._shape_of(q)[1] + len(r)) for q, r in zip(src, per)]
+        if info.pad:                                      # lpg_batch_info: a ragged batch
+            return RaggedBatchEngine(shapes, lib=self.lib, _handle=child)
+        return BatchEngine(len(src), shapes[0][0], shapes[0][1], lib=self.lib, _handle=child)
+
+    def _shape_of(self, q):
+        return self.m, self.ncols
+
 
 class RaggedBatchEngine(BatchEngine):
     """BatchEngine.ragged(shapes): LPs of different shapes in one batch
@@ -521,6 +569,9 @@ class RaggedBatchEngine(BatchEngine):
 
     def _child(self, handle, src):
         return RaggedBatchEngine([(self.shapes[q][0] + 1, self.shapes[q][1] + 1) for q in src], lib=self.lib, _handle=handle)
+
+    def _shape_of(self, q):
+        return self.shapes[q]
 
     def shape(self, lp: int) -> L.BatchShape:
         s = L.BatchShape()

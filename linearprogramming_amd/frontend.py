@@ -22,7 +22,9 @@ the reference binary's transcripts). Stages, each citing what it restates:
                    true unit column get artificials (two-phase or Big-M)
 * ``solve_ilp``    integer LPs (the reference's wish-list, README): branch and
                    bound whose node LPs are a batch, a level per
-                   BatchEngine.branch + solve_dual ("Branching")
+                   BatchEngine.branch + solve_dual ("Branching"),
+                   optionally after rounds of Gomory cuts at the root
+                   (BatchEngine.cut, DESIGN.md §3.7, "Cuts")
 
 The variable table mirrors hashTable.c (PutVarItem replaces an existing key in
 place; GetVarItems walks buckets in hash order, VarHash hashTable.c:148-167).
@@ -891,12 +893,18 @@ def integer_mask(sm: SMatrix, integer) -> np.ndarray:
 
 
 def solve_ilp(sm: SMatrix, integer, *, int_tol: float = 1e-6, node_limit: int = 100000, rule=None,
-              device: int = 0) -> ILPSolution:
+              device: int = 0, cut_rounds: int = 0, max_cuts: int = 8) -> ILPSolution:
     """Branch and bound on the device: the variables named in ``integer`` must be integers.
 
     Level-synchronous and breadth-first, fixed so that a CPU restatement follows it node for node
-    (tests/branch_cases.py reference_walk). The root is solved as solve() solves it (the primal simplex, or
-    two-phase where rows lack a basic column) in a batch of one. Then, per level: branch_select on the level's
+    (tests/branch_cases.py reference_walk; with cut rounds tests/cut_cases.py reference_walk). The root is solved
+    as solve() solves it (the primal simplex, or two-phase where rows lack a basic column) in a batch of one.
+    After an OPTIMAL root, up to ``cut_rounds`` rounds of Gomory mixed-integer cuts (include/lpg.h, "cuts"):
+    cut_select lists the root's ``max_cuts`` most fractional rows (none: the rounds end); cut() makes the batch of
+    one with those cuts and the parent is closed; solve_dual() re-optimises it, its pivots are added and it counts
+    as one more node; an INFEASIBLE result ends the call as INFEASIBLE and any other status but OPTIMAL ends it
+    with that status; the LP with its cuts is the root of the tree (depth 1). ``cut_rounds=0`` makes none of
+    these calls. Then, per level: branch_select on the level's
     batch (``rule``: BRANCH_MOST_FRACTIONAL by default); of the nodes with no fractional integer variable the
     best (larger max-form objective, then lower index) replaces the incumbent if strictly better; a remaining
     node whose objective is <= the incumbent's is dropped; every survivor gets two children, down before up,
@@ -925,6 +933,19 @@ def solve_ilp(sm: SMatrix, integer, *, int_tol: float = 1e-6, node_limit: int = 
         sol = ILPSolution(res[0].status_name, int(res[0].pivots), method=used, nodes=1, depth=1)
         if res[0].status != L.OPTIMAL:
             return sol
+        for _ in range(cut_rounds):
+            rows = batch.cut_select(mask, int_tol, max_cuts)[0]
+            if not len(rows):
+                break
+            child = batch.cut([0], [rows], mask)
+            batch.close()
+            batch = child
+            res = batch.solve_dual()
+            sol.nodes += 1
+            sol.pivots += int(res[0].pivots)
+            if res[0].status != L.OPTIMAL:
+                sol.status = res[0].status_name
+                return sol
         alive, objective = [0], [res[0].objective]           # the level: LPs of `batch`, their objectives
         best = None                                          # (objective, x_B, basis, ncols) of the incumbent
         while alive:
@@ -967,11 +988,12 @@ def solve_ilp(sm: SMatrix, integer, *, int_tol: float = 1e-6, node_limit: int = 
 
 
 def solve_ilp_text(text: str, integer=None, *, int_tol: float = 1e-6, node_limit: int = 100000, rule=None,
-                   device: int = 0) -> ILPSolution:
+                   device: int = 0, cut_rounds: int = 0, max_cuts: int = 8) -> ILPSolution:
     """LP text -> the integer optimum; ``integer=None``: every variable the text itself names."""
     if integer is None:
         integer = text_variables(text)
-    return solve_ilp(build_smatrix(text), integer, int_tol=int_tol, node_limit=node_limit, rule=rule, device=device)
+    return solve_ilp(build_smatrix(text), integer, int_tol=int_tol, node_limit=node_limit, rule=rule, device=device,
+                     cut_rounds=cut_rounds, max_cuts=max_cuts)
 
 
 def main(argv=None) -> int:

@@ -52,8 +52,19 @@ __host__ __device__ __forceinline__ int64_t unit_column(int64_t m, int64_t n, in
 // v[68:69]` overwriting the loaded piv before the conditional copy). So the
 // comparisons below are branch-free (bitwise & |, selects) and every "take"
 // is a per-field select on ONE predicate (cand_take / pp_take).
+//
+// cand_better is lpo.c's cand_less: (theta, key) lexicographic, and a NaN
+// theta (b = a = +inf; the dual's d = +inf, a = -inf) loses to every number
+// while two NaNs order by key. That makes the order total, so a thread's
+// strided loop, the xor butterfly and the waves' LDS pass all keep the same
+// winner; with plain `<` a NaN holder neither gave nor took, and the winner
+// depended on where the NaN row sat. block_argmin_cand's packed keys agree:
+// the bits of a NaN, whatever its sign, are above those of every theta >= 0
+// and below the invalid key ~0, and inf / inf gives one bit pattern only.
 __device__ __forceinline__ bool cand_better(const Cand &a, const Cand &b) {
-    const bool ord = (a.theta != b.theta) ? (a.theta < b.theta) : (a.key < b.key);
+    const bool an = a.theta != a.theta, bn = b.theta != b.theta;
+    const bool lt = a.theta < b.theta, same = (a.theta == b.theta) | (an & bn);
+    const bool ord = lt | (!an & bn) | (same & (a.key < b.key));
     return (a.row >= 0) & ((b.row < 0) | ord);
 }
 

@@ -226,10 +226,16 @@ static int64_t price(const lpo_ctx *c, int rule) {
 
 typedef struct { double theta; int64_t key; int64_t row; } cand_t;
 
+/* A NaN ratio (b = a = +inf) loses to every number and two NaNs order by
+ * key, so the order is total and the winner does not depend on the order in
+ * which the candidates meet (rows of one block, blocks of lpo_solve's nparts,
+ * the lanes and waves of the device's reductions). */
 static int cand_less(const cand_t *a, const cand_t *b) {
     if (a->row < 0) return 0;
     if (b->row < 0) return 1;
-    if (a->theta != b->theta) return a->theta < b->theta;
+    const int an = a->theta != a->theta, bn = b->theta != b->theta;
+    if (an != bn) return bn;
+    if (!an && a->theta != b->theta) return a->theta < b->theta;
     return a->key < b->key;
 }
 
@@ -477,7 +483,8 @@ int lpo_solve_dual(lpo_ctx *c, int64_t max_pivots, lpo_result *out) {
             const double a = row[j];
             if (!(a < -c->eps_piv)) continue;
             const double v = d[j] > 0.0 ? d[j] / -a : 0.0;
-            if (k < 0 || v < best) { k = j; best = v; }
+            /* a NaN ratio (d_j = +inf, a = -inf) loses to every number, as in cand_less */
+            if (k < 0 || v < best || (best != best && v == v)) { k = j; best = v; }
         }
         if (k < 0) { status = LPO_INFEASIBLE; break; }
         if (lpo_pivot(c, k, r) != 0) return -1;

@@ -4,8 +4,8 @@ run the other tier and the small chunks here.
 
     python batch_worker.py CASES SPECS.json OUT.npz
 
-CASES: the module the specs belong to (batch_cases, batch2_cases or
-batch3_cases); SPECS.json: a list of its specs; OUT.npz: its run_batch's arrays
+CASES: the module the specs belong to (batch_cases, batch2_cases,
+batch3_cases, tie_cases, ...); SPECS.json: a list of its specs; OUT.npz: its run_batch's arrays
 of case i under the prefix "i/".
 """
 import importlib

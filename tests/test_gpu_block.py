@@ -244,11 +244,13 @@ def test_reload_into_a_solved_context(lpg, monkeypatch):
 
 
 @pytest.mark.parametrize("persist", [None, 0])
-@pytest.mark.parametrize("case", ["nan_b", "inf_b", "overflowing_ratio"])
+@pytest.mark.parametrize("case", ["nan_b", "inf_b", "overflowing_ratio", "nan_ratio", "nan_ratio_only"])
 def test_numeric_rule_matches_oracle(lpg, monkeypatch, persist, case):
     """The oracle stops NUMERIC when the chosen row's pivot element or b is not
     finite (oracle/lpo.c lpo_solve) and otherwise pivots, an overflowing
-    ratio b / a included: the persistent kernel and the pair agree."""
+    ratio b / a included: the persistent kernel and the pair agree. A NaN
+    ratio (b = a = +inf) loses to every number wherever its row sits, and two
+    NaN ratios order by key (cand_better, lpo.c cand_less)."""
     m, n = 60, 90
     o = Oracle(m, n + m + 1)
     o.generate(n, 5, 0)
@@ -258,9 +260,19 @@ def test_numeric_rule_matches_oracle(lpg, monkeypatch, persist, case):
         T[7, 0] = np.nan
     elif case == "inf_b":
         T[7, 0] = -np.inf
-    else:                                      # b finite, b / a overflows for the entering column
+    elif case == "overflowing_ratio":          # b finite, b / a overflows for the entering column
         T[7, 0] = 1e308
         T[7, 1:n + 1] = 1e-10
+    elif case == "nan_ratio":                  # column 1 enters; row 1's ratio is NaN, row 33 holds the least
+        T[:m, 1] = 1.0
+        T[:m, 0] = 2.0 + np.arange(m)
+        T[33, 0] = 0.5
+        T[1, 0] = T[1, 1] = np.inf
+        T[m, 1] = -100.0
+    else:                                      # nan_ratio_only: every eligible row of column 1 has a NaN ratio
+        T[:m, 1] = 0.0
+        T[[5, 9], 0] = T[[5, 9], 1] = np.inf
+        T[m, 1] = -100.0
     o2 = Oracle(m, n + m + 1)
     o2.load_tableau(T, basis)
     ores = o2.solve(1000, 0)
@@ -269,6 +281,36 @@ def test_numeric_rule_matches_oracle(lpg, monkeypatch, persist, case):
     res = e.solve(1000, 0)
     assert res.status == ores.status and res.pivots == ores.pivots
     assert _log(e) == _log(o2)
+    if case == "nan_ratio":
+        assert _log(o2)[0] == (1, 33)
+    if case == "nan_ratio_only":
+        assert (ores.status, ores.pivots) == (5, 0)
+
+
+@pytest.mark.parametrize("rule", [0, 1])
+@pytest.mark.parametrize("nan_row", [0, 1, 59])
+def test_nan_ratio_on_the_eager_kernels(lpg, nan_row, rule):
+    """LPG_FLAG_EAGER's k_select keeps its candidates in block_reduce_cand's
+    xor butterfly, where a lane that held a NaN ratio neither gave nor took
+    before cand_better ordered NaNs last: row 33 holds the least ratio and
+    wins wherever the NaN row (b = a = +inf) sits."""
+    m, n = 60, 90
+    o = Oracle(m, n + m + 1)
+    o.generate(n, 5, 0)
+    T = o.get_rows().copy()
+    basis = np.arange(n + 1, n + m + 1, dtype=np.int64)
+    T[:m, 1] = 1.0
+    T[:m, 0] = 2.0 + np.arange(m)
+    T[33, 0] = 0.5
+    T[nan_row, 0] = T[nan_row, 1] = np.inf
+    T[m, 1] = -100.0
+    o.load_tableau(T, basis)
+    ores = o.solve(1000, rule)
+    e = lpg.Engine(m, n + m + 1, flags=lpg._lib.FLAG_EAGER)
+    e.load_tableau(T, basis)
+    res = e.solve(1000, rule)
+    assert res.status == ores.status and res.pivots == ores.pivots
+    assert _log(e) == _log(o) and _log(o)[0] == (1, 33)
 
 
 def _tied_lp(m, n, seed):

@@ -41,16 +41,20 @@
 // of the solve kernels, says which of the two a launch is: a uniform batch
 // runs the instantiations it ran before there were ragged ones.
 //
-// Branching (lpg_batch_branch_select, lpg_batch_branch): the step between two
-// levels of a branch-and-bound tree whose node LPs are a batch.
-// k_batch_branch_select picks every LP's branching row over its basis;
-// k_batch_branch makes the batch of the children, each its parent's tableau
-// plus one bound row and one slack column, by a copy in device memory.
-//
-// Cuts (lpg_batch_cut_select, lpg_batch_cut): a round of Gomory mixed-integer
-// cuts on a batch. k_batch_cut_select lists every LP's most fractional rows;
-// k_batch_cut makes the batch of the children, each its parent's tableau plus
-// one cut row and one slack column per listed row, by the same kind of copy.
+// Branching (lpg_batch_branch_select, lpg_batch_branch) and cuts
+// (lpg_batch_cut_select, lpg_batch_cut): the step between two levels of a
+// branch-and-bound tree whose node LPs are a batch, and a round of Gomory
+// mixed-integer cuts on a batch. Both are one path with two policies.
+// Selection: frac_candidate says what a fractional row of the basis is;
+// k_batch_branch_select picks every LP's best one, k_batch_cut_select lists
+// its most fractional ones. Children: grow_copy makes a child from its
+// parent's tableau plus k rows and k slack columns by a copy in device memory;
+// k_batch_branch calls it with the one bound row, k_batch_cut, behind a
+// prologue in LDS of its own, with one cut row per listed row. On the host
+// stage_mask uploads the integer mask of all three calls that take one,
+// grow_create makes the child batch and grow_finish launches the copy; what
+// lpg_batch_branch and lpg_batch_cut keep is their own argument checks and
+// job arrays.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -178,6 +182,11 @@ __device__ __forceinline__ LpGeo lp_geo(const BatchGeo &g, int64_t lp, int64_t n
     return s;
 }
 
+// geometry of LP `lp` of a plain batch, whatever its layout: for the kernels that are not built per layout
+__device__ __forceinline__ LpGeo lp_geo_any(const BatchGeo &g, int64_t lp) {
+    return g.shape ? lp_geo<true>(g, lp, 1, 0) : lp_geo<false>(g, lp, 1, 0);
+}
+
 // ------------------------------------------------------------------------
 // generator: LP b = lpo_generate(n, seed + b, kind), one block per row
 // ------------------------------------------------------------------------
@@ -250,7 +259,7 @@ __global__ void k_batch_begin_two_phase(BatchLP *lp, int64_t count, int64_t budg
 // (workgroup b looks at LP b, whatever the order of the solve launches)
 __global__ __launch_bounds__(kBlock) void k_batch_dual_check(BatchGeo g, unsigned long long *bad) {
     const int64_t b = blockIdx.x;
-    const LpGeo s = g.shape ? lp_geo<true>(g, b, 1, 0) : lp_geo<false>(g, b, 1, 0);
+    const LpGeo s = lp_geo_any(g, b);
     const double *obj = g.T + s.t_off + s.m * s.ld;
     bool any = false;
     for (int64_t j = 1 + threadIdx.x; j <= s.nact; j += kBlock) any |= obj[j] < -g.eps_opt;
@@ -736,7 +745,7 @@ __global__ __launch_bounds__(kBlock) void k_batch_big_m(BatchGeo g, TwoPhase t) 
 // lpo_set_objective on every LP, costs as k_batch_two_phase's (count x N)
 __global__ __launch_bounds__(kBlock) void k_batch_set_objective(BatchGeo g, const double *costs) {
     const int64_t b = blockIdx.x;
-    const LpGeo s = g.shape ? lp_geo<true>(g, b, 1, 0) : lp_geo<false>(g, b, 1, 0);
+    const LpGeo s = lp_geo_any(g, b);
     const int64_t m = s.m, ld = s.ld;
     double *T = g.T + s.t_off;
     const int64_t *gB = g.basis + s.b_off;
@@ -760,29 +769,38 @@ struct BranchPick {           // lpg_branch_t
 };
 static_assert(sizeof(BranchPick) == sizeof(lpg_branch_t), "BranchPick is lpg_branch_t");
 
-// The branching row of LP blockIdx.x: over the rows whose basic column is
-// integer-constrained (mask, nmask bytes per LP at pitch ld_mask, 0: one for
-// all), the candidates are those with dist = min(f, 1 - f) > int_tol,
-// f = v - floor(v), v = T[i][0]. A candidate is a pricing partial (v = -dist
-// < 0, j = its column, pad = its row), so the block argmin of the solve
-// kernels picks it: RULE_DANTZIG the largest dist, ties -> the smallest
-// column; RULE_BLAND the smallest column (the basic columns of an LP differ).
+// Row i as a candidate of the select kernels: a row whose basic column bj is
+// integer-constrained (mk, the LP's nmask mask bytes) is one when
+// dist = min(f, 1 - f) > int_tol, f = v - floor(v), v = T[i][0], and the
+// caller's also(-dist, bj) holds. A candidate is a pricing partial (v = -dist
+// < 0, j = its column, pad = its row; j = -1: none), so the block argmin of
+// the solve kernels picks among them: RULE_DANTZIG the largest dist, ties ->
+// the smallest column; RULE_BLAND the smallest column (the basic columns of
+// an LP differ).
+template <class Also>
+__device__ __forceinline__ PricePart frac_candidate(const int64_t *gB, const double *T, int64_t ld, const uint8_t *mk,
+                                                    int64_t nmask, double int_tol, int64_t i, Also also) {
+    const int64_t bj = gB[i];
+    const bool integer = (bj >= 1) & (bj <= nmask) && mk[bj - 1] != 0;
+    const double v = T[i * ld];
+    const double f = v - floor(v), f1 = 1.0 - f;
+    const double dist = f < f1 ? f : f1;
+    return PricePart{-dist, (integer & (dist > int_tol) & also(-dist, bj)) ? bj : -1, 0, (int32_t)i};
+}
+
+// The branching row of LP blockIdx.x: the best candidate under RULE (mask:
+// nmask bytes per LP at pitch ld_mask, 0: one for all)
 template <int RULE>
 __global__ __launch_bounds__(kBlock) void k_batch_branch_select(BatchGeo g, const uint8_t *mask, int64_t nmask, int64_t ld_mask,
                                                                 double int_tol, BranchPick *out) {
     const int64_t q = blockIdx.x;
-    const LpGeo s = g.shape ? lp_geo<true>(g, q, 1, 0) : lp_geo<false>(g, q, 1, 0);
+    const LpGeo s = lp_geo_any(g, q);
     const double *T = g.T + s.t_off;
     const int64_t *gB = g.basis + s.b_off;
     const uint8_t *mk = mask + q * ld_mask;
     PricePart pb{0.0, -1, 0, 0};
     for (int64_t i = threadIdx.x; i < s.m; i += kBlock) {
-        const int64_t bj = gB[i];
-        const bool integer = (bj >= 1) & (bj <= nmask) && mk[bj - 1] != 0;
-        const double v = T[i * s.ld];
-        const double f = v - floor(v), f1 = 1.0 - f;
-        const double dist = f < f1 ? f : f1;
-        PricePart c{-dist, (integer & (dist > int_tol)) ? bj : -1, 0, (int32_t)i};
+        const PricePart c = frac_candidate(gB, T, s.ld, mk, nmask, int_tol, i, [](double, int64_t) { return true; });
         pp_take(pb, c, pp_better<RULE>(c, pb));
     }
     pb = block_argmin_pp<RULE>(pb);
@@ -801,71 +819,90 @@ struct BranchJob {            // child c of lpg_batch_branch: validated on the h
     int32_t src, row, dir, pad;
 };
 
-// entry (i, j) of the child, j a column of the unshifted part (0..nact: the
-// parent's column j), from the parent's entry x of the source row: a copy, or
-// in the new row `m` one negation; its right-hand side and the zero in the
-// branching variable's own column are exact
-__device__ __forceinline__ double branch_entry(double x, bool newrow, int64_t j, int64_t bj, bool down, double rhs) {
-    if (!newrow) return x;
+// entry j of a bound row from the branching row's entry x in column j of the
+// parent: one negation; the right-hand side and the zero in the branching
+// variable's own column bj are exact
+__device__ __forceinline__ double branch_entry(double x, int64_t j, int64_t bj, bool down, double rhs) {
     const double y = down ? -x : x;
     return j == 0 ? rhs : (j == bj ? 0.0 : y);
 }
 
-// Child blockIdx.x of `c` from LP job.src of `p` (RG: both ragged, as the
-// parent is). A copy kernel: the parent's tableau is streamed from device memory
-// row by row into the child's rows at the child's pitch. Columns 0..nact keep
-// their place: both pitches are multiples of 64 doubles and both tableaus
-// start on one, so the even part of them moves as 16-byte loads and stores,
-// consecutive lanes on consecutive pairs of a row. The rest of a row (the new
-// slack column nact + 1, behind it the parent's columns nact + 1.. one to the
-// right) moves as doubles. The child's padding columns stay the zeros of its
-// allocation.
-template <bool RG>
-__global__ __launch_bounds__(kBlock) void k_batch_branch(BatchGeo p, BatchGeo c, const BranchJob *jobs) {
-    const BranchJob job = jobs[blockIdx.x];
-    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0), cs = lp_geo<RG>(c, blockIdx.x, 1, 0);
+// The copy that makes a child of branching or of a round of cuts: the child
+// (c, cs) is the parent (p, ps) plus k rows behind its rows and k slack
+// columns behind its active ones. Child row i is the parent's row i (i < m),
+// new row t = i - m (m <= i < m + k) or the parent's objective row
+// (i = m + k); new row t is made from the parent's row src_row(t), entry by
+// entry: row_entry(t), asked for once per row and lane, is the function that
+// gives its entry from that row's x in the parent's column j as (x, j). The
+// parent's tableau is streamed from device memory row by row into the child's
+// rows at the child's pitch. Columns 0..nact keep their place: both pitches
+// are multiples of 64 doubles and both tableaus start on one, so the even part
+// of them moves as 16-byte loads and stores, consecutive lanes on consecutive
+// pairs of a row. The rest of a row (the k slack columns nact + 1.., new row
+// t's 1 in slack t; behind them the parent's columns nact + 1.. moved right
+// by k, which an odd k takes off the 16-byte grid) moves as doubles. The
+// child's padding columns stay the zeros of its allocation. The child's basis
+// is the parent's with the same shift, and slack t basic in new row t.
+template <class SrcRow, class RowEntry>
+__device__ __forceinline__ void grow_copy(const BatchGeo &p, const LpGeo &ps, const BatchGeo &c, const LpGeo &cs, int64_t k,
+                                          SrcRow src_row, RowEntry row_entry) {
     const double *pT = p.T + ps.t_off;
     double *cT = c.T + cs.t_off;
     const int64_t *pB = p.basis + ps.b_off;
     int64_t *cB = c.basis + cs.b_off;
-    const int64_t m = ps.m, nc = ps.ncols, nact = ps.nact, pld = ps.ld, cld = cs.ld, r = job.row;
-    const bool down = job.dir < 0;
-    const double v = pT[r * pld];
-    const int64_t bj = pB[r];
-    const double rhs = down ? floor(v) - v : v - ceil(v);
+    const int64_t m = ps.m, nc = ps.ncols, nact = ps.nact, pld = ps.ld, cld = cs.ld;
     const int tid = threadIdx.x;
 
     // a tile of 1 << txs lanes along a row (enough for its pairs, 256 at the most) and 256 >> txs rows at a
-    // time: the row and column of a lane come from shifts, and a narrow LP still fills the workgroup.
-    // child row i comes from the parent's row i (i < m), `r` (the new row m) or m (the objective, now row m + 1)
+    // time: the row and column of a lane come from shifts, and a narrow LP still fills the workgroup
     const int npair = (int)((nact + 1) >> 1), w0 = 2 * npair;      // columns [0, w0) as pairs
     int txs = 0;
     while ((1 << txs) < npair && txs < 8) txs++;
     const int tx = 1 << txs, ty = kBlock >> txs, j0 = tid & (tx - 1), i0 = tid >> txs;
-    for (int64_t i = i0; i < m + 2; i += ty) {
-        const int64_t si = i < m ? i : (i == m ? r : m);
+    for (int64_t i = i0; i < m + k + 1; i += ty) {
+        const bool fresh = (i >= m) & (i < m + k);
+        const int64_t t = fresh ? i - m : 0;
+        const int64_t si = i < m ? i : (fresh ? (int64_t)src_row(t) : m);
+        const auto entry = row_entry(t);                           // row 0's on a copied row, where it is not called
         const double *prow = pT + si * pld;
         double *crow = cT + i * cld;
-        const bool newrow = i == m;
         for (int j = 2 * j0; j < w0; j += 2 * tx) {
-            const d2 x = *(const d2 *)(prow + j);
-            d2 y;
-            y.x = branch_entry(x.x, newrow, j, bj, down, rhs);
-            y.y = branch_entry(x.y, newrow, j + 1, bj, down, rhs);
-            *(d2 *)(crow + j) = y;
+            d2 x = *(const d2 *)(prow + j);
+            if (fresh) {
+                x.x = entry(x.x, j);
+                x.y = entry(x.y, (int64_t)j + 1);
+            }
+            *(d2 *)(crow + j) = x;
         }
-        // child columns [w0, nc]: at most one unshifted column, the slack, the shifted columns
-        for (int64_t j = w0 + j0; j <= nc; j += tx) {
+        // child columns [w0, nc + k): at most one unshifted column, the slacks, the shifted columns
+        for (int64_t j = w0 + j0; j < nc + k; j += tx) {
             double y;
-            if (j == nact + 1) y = newrow ? 1.0 : 0.0;
+            if (j > nact && j <= nact + k) y = (fresh && j == nact + 1 + t) ? 1.0 : 0.0;
             else {
-                const int64_t pj = j <= nact ? j : j - 1;
-                y = branch_entry(prow[pj], newrow, pj, bj, down, rhs);
+                const int64_t pj = j <= nact ? j : j - k;
+                y = prow[pj];
+                if (fresh) y = entry(y, pj);
             }
             crow[j] = y;
         }
     }
-    for (int64_t i = tid; i <= m; i += kBlock) cB[i] = i == m ? nact + 1 : (pB[i] > nact ? pB[i] + 1 : pB[i]);
+    for (int64_t i = tid; i < m + k; i += kBlock) cB[i] = i >= m ? nact + 1 + (i - m) : (pB[i] > nact ? pB[i] + k : pB[i]);
+}
+
+// Child blockIdx.x of `c` from LP job.src of `p` (RG: both ragged, as the
+// parent is): grow_copy by the one bound row, made from the branching row.
+// No LDS and nothing in front of the copy.
+template <bool RG>
+__global__ __launch_bounds__(kBlock) void k_batch_branch(BatchGeo p, BatchGeo c, const BranchJob *jobs) {
+    const BranchJob job = jobs[blockIdx.x];
+    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0), cs = lp_geo<RG>(c, blockIdx.x, 1, 0);
+    const int64_t r = job.row;
+    const bool down = job.dir < 0;
+    const double v = p.T[ps.t_off + r * ps.ld];
+    const int64_t bj = p.basis[ps.b_off + r];
+    const double rhs = down ? floor(v) - v : v - ceil(v);
+    grow_copy(p, ps, c, cs, 1, [&](int64_t) { return r; },
+              [&](int64_t) { return [&](double x, int64_t j) { return branch_entry(x, j, bj, down, rhs); }; });
 }
 
 // ------------------------------------------------------------------------
@@ -882,14 +919,15 @@ __device__ __forceinline__ double cut_frac(double x) {
     return f >= 1.0 ? 0.0 : f;
 }
 
-// The cut rows of LP blockIdx.x: branch_select's candidates, the `max_cuts`
-// best in LPG_BRANCH_MOST_FRACTIONAL order, by repeated extraction: round t
-// takes the block argmin over the candidates that come strictly behind pick
-// t - 1 in that order (a total one: the basic columns of an LP differ).
+// The cut rows of LP blockIdx.x: the candidates of k_batch_branch_select
+// (frac_candidate), the `max_cuts` best in LPG_BRANCH_MOST_FRACTIONAL order,
+// by repeated extraction: round t takes the block argmin over the candidates
+// that come strictly behind pick t - 1 in that order (a total one: the basic
+// columns of an LP differ).
 __global__ __launch_bounds__(kBlock) void k_batch_cut_select(BatchGeo g, const uint8_t *mask, int64_t nmask, int64_t ld_mask,
                                                              double int_tol, int64_t max_cuts, int64_t *ncut, int64_t *rows) {
     const int64_t q = blockIdx.x;
-    const LpGeo s = g.shape ? lp_geo<true>(g, q, 1, 0) : lp_geo<false>(g, q, 1, 0);
+    const LpGeo s = lp_geo_any(g, q);
     const double *T = g.T + s.t_off;
     const int64_t *gB = g.basis + s.b_off;
     const uint8_t *mk = mask + q * ld_mask;
@@ -898,14 +936,9 @@ __global__ __launch_bounds__(kBlock) void k_batch_cut_select(BatchGeo g, const u
     int64_t last_j = -1, t = 0;
     for (; t < max_cuts; t++) {
         PricePart pb{0.0, -1, 0, 0};
+        auto behind = [&](double v, int64_t bj) { return (t == 0) | (v > last_v) | ((v == last_v) & (bj > last_j)); };
         for (int64_t i = threadIdx.x; i < s.m; i += kBlock) {
-            const int64_t bj = gB[i];
-            const bool integer = (bj >= 1) & (bj <= nmask) && mk[bj - 1] != 0;
-            const double v = T[i * s.ld];
-            const double f = v - floor(v), f1 = 1.0 - f;
-            const double dist = f < f1 ? f : f1;
-            const bool behind = (t == 0) | (-dist > last_v) | ((-dist == last_v) & (bj > last_j));
-            PricePart c{-dist, (integer & (dist > int_tol) & behind) ? bj : -1, 0, (int32_t)i};
+            const PricePart c = frac_candidate(gB, T, s.ld, mk, nmask, int_tol, i, behind);
             pp_take(pb, c, pp_better<RULE_DANTZIG>(c, pb));
         }
         pb = block_argmin_pp<RULE_DANTZIG>(pb);
@@ -938,14 +971,9 @@ __device__ __forceinline__ double cut_entry(double a, int64_t j, int64_t nact, c
 
 // Child blockIdx.x of `c` from LP job.src of `p` (RG: the parent is ragged,
 // and then the child is; a parent of one shape has a ragged child where the
-// cut counts differ). k_batch_branch's streaming copy with k new rows and k
-// new columns: the prologue marks the source's basic columns in an LDS byte
-// map and computes (f0, rho) of every cut; then columns 0..nact keep their
-// place and move as 16-byte pairs, and the rest of a row (the k slack columns
-// nact + 1.., behind them the parent's columns nact + 1.. moved right by k,
-// which an odd k takes off the 16-byte grid) moves as doubles. Child row i is
-// the parent's row i (i < m), the cut from row sRow[i - m] (m <= i < m + k) or
-// the parent's objective row (i = m + k).
+// cut counts differ). The prologue marks the source's basic columns in an LDS
+// byte map and computes (f0, rho) of every cut; then grow_copy by the job's k
+// cut rows, cut t made from row sRow[t].
 template <bool RG>
 __global__ __launch_bounds__(kBlock) void k_batch_cut(BatchGeo p, BatchGeo c, const CutJob *jobs, const int32_t *rows,
                                                       const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
@@ -955,20 +983,17 @@ __global__ __launch_bounds__(kBlock) void k_batch_cut(BatchGeo p, BatchGeo c, co
     uint8_t *sBasic = (uint8_t *)sBasicWords;
 
     const CutJob job = jobs[blockIdx.x];
-    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0);
-    const LpGeo cs = (RG || c.shape) ? lp_geo<true>(c, blockIdx.x, 1, 0) : lp_geo<false>(c, blockIdx.x, 1, 0);
+    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0), cs = lp_geo_any(c, blockIdx.x);
     const double *pT = p.T + ps.t_off;
-    double *cT = c.T + cs.t_off;
     const int64_t *pB = p.basis + ps.b_off;
-    int64_t *cB = c.basis + cs.b_off;
     const uint8_t *mk = mask + (int64_t)job.src * ld_mask;
-    const int64_t m = ps.m, nc = ps.ncols, nact = ps.nact, pld = ps.ld, cld = cs.ld, k = job.k;
+    const int64_t m = ps.m, nc = ps.ncols, nact = ps.nact, k = job.k;
     const int tid = threadIdx.x;
 
     for (int64_t w = tid; w < (nc + 3) >> 2; w += kBlock) sBasicWords[w] = 0;
     for (int64_t t = tid; t < k; t += kBlock) {
         const int32_t r = rows[job.first + t];
-        const double f0 = cut_frac(pT[r * pld]);
+        const double f0 = cut_frac(pT[r * ps.ld]);
         sRow[t] = r;
         sF0[t] = f0;
         sRho[t] = __ddiv_rn(f0, 1.0 - f0);
@@ -980,38 +1005,10 @@ __global__ __launch_bounds__(kBlock) void k_batch_cut(BatchGeo p, BatchGeo c, co
     }
     __syncthreads();
 
-    const int npair = (int)((nact + 1) >> 1), w0 = 2 * npair;      // columns [0, w0) as pairs
-    int txs = 0;
-    while ((1 << txs) < npair && txs < 8) txs++;
-    const int tx = 1 << txs, ty = kBlock >> txs, j0 = tid & (tx - 1), i0 = tid >> txs;
-    for (int64_t i = i0; i < m + k + 1; i += ty) {
-        const bool cut = (i >= m) & (i < m + k);
-        const int64_t t = cut ? i - m : 0;
-        const int64_t si = i < m ? i : (cut ? (int64_t)sRow[t] : m);
-        const double f0 = sF0[t], rho = sRho[t];               // read only where `cut`
-        const double *prow = pT + si * pld;
-        double *crow = cT + i * cld;
-        for (int j = 2 * j0; j < w0; j += 2 * tx) {
-            d2 x = *(const d2 *)(prow + j);
-            if (cut) {
-                x.x = cut_entry(x.x, j, nact, sBasic, mk, nmask, f0, rho);
-                x.y = cut_entry(x.y, j + 1, nact, sBasic, mk, nmask, f0, rho);
-            }
-            *(d2 *)(crow + j) = x;
-        }
-        // child columns [w0, nc + k): at most one unshifted column, the slacks, the shifted columns
-        for (int64_t j = w0 + j0; j < nc + k; j += tx) {
-            double y;
-            if (j > nact && j <= nact + k) y = (cut && j == nact + 1 + t) ? 1.0 : 0.0;
-            else {
-                const int64_t pj = j <= nact ? j : j - k;
-                y = prow[pj];
-                if (cut) y = cut_entry(y, pj, nact, sBasic, mk, nmask, f0, rho);
-            }
-            crow[j] = y;
-        }
-    }
-    for (int64_t i = tid; i < m + k; i += kBlock) cB[i] = i >= m ? nact + 1 + (i - m) : (pB[i] > nact ? pB[i] + k : pB[i]);
+    grow_copy(p, ps, c, cs, k, [&](int64_t t) { return sRow[t]; }, [&](int64_t t) {
+        const double f0 = sF0[t], rho = sRho[t];
+        return [=](double a, int64_t j) { return cut_entry(a, j, nact, sBasic, mk, nmask, f0, rho); };
+    });
 }
 
 }  // namespace lpg
@@ -1304,64 +1301,54 @@ int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_res
     return 0;
 }
 
-// lpg_batch_solve_two_phase (M_TWO_PHASE) and lpg_batch_solve_big_m (M_BIG_M); `call` names the entry point
-int solve_artificial(lpg_batch *b, Method method, const char *call, int64_t art_first, const double *cost, int64_t ld_cost,
-                     int64_t max_pivots, int rule, lpg_result *out) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
-    if ((b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
-    if (b->ragged)
-        return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m_ragged" : "lpg_batch_solve_two_phase_ragged");
-    const int64_t N = b->ncols - 1;
-    if (art_first < 2 || art_first > N)
-        return bfail(b, LPG_ERR_ARG, "%s: art_first %lld outside 2..%lld", call, (long long)art_first, (long long)N);
-    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
-    if (cost && ld_cost < N)
-        return bfail(b, LPG_ERR_ARG, "%s: ld_cost %lld < N = %lld", call, (long long)ld_cost, (long long)N);
-    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
-    BHIPCHK(b, hipSetDevice(b->device));
-    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
-    TwoPhase t{};
-    t.cost = b->cost;
-    t.art_first = art_first;
-    t.max_pivots = max_pivots;
-    t.save_cost = cost ? 0 : 1;
-    // two-phase: what phase II prices, and what a later lpg_batch_solve goes on with; Big-M prices all of 1..N
-    if (method == M_TWO_PHASE) b->nact = art_first - 1;
-    return batch_run(b, max_pivots, method, rule, out, t);
-}
-
 // the records of a ragged batch to the device (after nact or art_first changed)
 int push_shapes(lpg_batch *b) {
     BHIPCHK(b, hipMemcpy(b->dshape, b->shape.data(), b->shape.size() * sizeof(BatchShape), hipMemcpyHostToDevice));
     return 0;
 }
 
-// lpg_batch_solve_two_phase_ragged and lpg_batch_solve_big_m_ragged: solve_artificial with one
-// art_first per LP and packed costs
-int solve_artificial_ragged(lpg_batch *b, Method method, const char *call, const int64_t *art_first, const double *cost,
-                            int64_t max_pivots, int rule, lpg_result *out) {
+// lpg_batch_solve_two_phase and lpg_batch_solve_big_m (M_TWO_PHASE, M_BIG_M; art_first points to the one
+// value, cost has pitch ld_cost) and their _ragged forms (`packed`: one art_first per LP, packed costs);
+// `call` names the entry point
+int solve_artificial(lpg_batch *b, Method method, const char *call, bool packed, const int64_t *art_first,
+                     const double *cost, int64_t ld_cost, int64_t max_pivots, int rule, lpg_result *out) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
     if ((b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
-    if (!b->ragged) return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m" : "lpg_batch_solve_two_phase");
-    if (!art_first) return bfail(b, LPG_ERR_ARG, "%s: art_first is NULL", call);
-    for (int64_t q = 0; q < b->count; q++)
-        if (art_first[q] < 2 || art_first[q] > b->shape[(size_t)q].ncols - 1)
-            return bfail(b, LPG_ERR_ARG, "%s: art_first %lld of LP %lld outside 2..%lld", call, (long long)art_first[q],
-                         (long long)q, (long long)(b->shape[(size_t)q].ncols - 1));
+    if (b->ragged != packed) {
+        if (packed) return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m" : "lpg_batch_solve_two_phase");
+        return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m_ragged" : "lpg_batch_solve_two_phase_ragged");
+    }
+    const int64_t N = b->ncols - 1;
+    if (packed) {
+        if (!art_first) return bfail(b, LPG_ERR_ARG, "%s: art_first is NULL", call);
+        for (int64_t q = 0; q < b->count; q++)
+            if (art_first[q] < 2 || art_first[q] > b->shape[(size_t)q].ncols - 1)
+                return bfail(b, LPG_ERR_ARG, "%s: art_first %lld of LP %lld outside 2..%lld", call, (long long)art_first[q],
+                             (long long)q, (long long)(b->shape[(size_t)q].ncols - 1));
+    } else if (*art_first < 2 || *art_first > N) {
+        return bfail(b, LPG_ERR_ARG, "%s: art_first %lld outside 2..%lld", call, (long long)*art_first, (long long)N);
+    }
     if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    if (!packed && cost && ld_cost < N)
+        return bfail(b, LPG_ERR_ARG, "%s: ld_cost %lld < N = %lld", call, (long long)ld_cost, (long long)N);
     if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
     BHIPCHK(b, hipSetDevice(b->device));
-    if (int rc = stage_costs(b, cost, 0)) return rc;
-    for (int64_t q = 0; q < b->count; q++) {
-        b->shape[(size_t)q].art_first = (int32_t)art_first[q];
-        // two-phase: what phase II prices, and what a later lpg_batch_solve goes on with
-        if (method == M_TWO_PHASE) b->shape[(size_t)q].nact = (int32_t)art_first[q] - 1;
-    }
-    if (int rc = push_shapes(b)) return rc;
+    if (int rc = stage_costs(b, cost, ld_cost)) return rc;
     TwoPhase t{};
     t.cost = b->cost;
     t.max_pivots = max_pivots;
     t.save_cost = cost ? 0 : 1;
+    // two-phase: nact is what phase II prices, and what a later lpg_batch_solve goes on with; Big-M prices all of 1..N
+    if (packed) {
+        for (int64_t q = 0; q < b->count; q++) {
+            b->shape[(size_t)q].art_first = (int32_t)art_first[q];
+            if (method == M_TWO_PHASE) b->shape[(size_t)q].nact = (int32_t)art_first[q] - 1;
+        }
+        if (int rc = push_shapes(b)) return rc;
+    } else {
+        t.art_first = *art_first;
+        if (method == M_TWO_PHASE) b->nact = *art_first - 1;
+    }
     return batch_run(b, max_pivots, method, rule, out, t);
 }
 
@@ -1639,8 +1626,96 @@ int mask_ok(lpg_batch *b, const char *call, int64_t nmask, int64_t ld_mask) {
     return 0;
 }
 
-int branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
-                  lpg_branch_t *out) {
+// The masks of a call on the device, for the kernels that read mask[q * pitch + j - 1] for j <= nmask only:
+// `count` masks packed at pitch nmask, or the one for all at pitch 0 (ld_mask = 0), uploaded on `stream`.
+// hipErrorOutOfMemory: the allocation failed (the caller's message names what it allocates beside it).
+hipError_t stage_mask(DevBuf &dmask, int64_t &pitch, const uint8_t *mask, int64_t nmask, int64_t ld_mask, int64_t count,
+                      hipStream_t stream) {
+    const int64_t nrows = ld_mask ? count : 1;
+    pitch = ld_mask ? nmask : 0;
+    if (hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess) return hipErrorOutOfMemory;
+    return hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask, (size_t)nrows,
+                            hipMemcpyHostToDevice, stream);
+}
+
+// src[c] of lpg_batch_branch and lpg_batch_cut names an LP of the parent
+int src_ok(lpg_batch *p, const char *call, int64_t c, int64_t src) {
+    if (src < 0 || src >= p->count)
+        return bfail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c, (long long)src,
+                     (long long)(p->count - 1));
+    return 0;
+}
+
+// a child batch that will not be returned: its message to the parent and the thread, and away with it
+int child_die(lpg_batch *p, lpg_batch *ch, int code) {
+    snprintf(g_berr, sizeof g_berr, "%s", ch->err);
+    snprintf(p->err, sizeof p->err, "%s", ch->err);
+    lpg_batch_destroy(ch);
+    return code;
+}
+
+// The child batch of lpg_batch_branch and lpg_batch_cut (`call`), its tableaus still zero: child c is LP src[c]
+// of `p` (checked) with k[c] more rows, columns and active columns, in a batch of the parent's flags and
+// tolerances; ragged when the parent is or the k[c] differ
+int grow_create(lpg_batch **out, lpg_batch *p, const char *call, int64_t n, const int64_t *src, const int64_t *k) {
+    const bool ragged = p->ragged || !std::all_of(k, k + n, [&](int64_t x) { return x == k[0]; });
+    lpg_batch *ch = nullptr;
+    int rc;
+    if (ragged) {
+        std::vector<int64_t> ms((size_t)n), ncs((size_t)n);
+        for (int64_t c = 0; c < n; c++) ms[(size_t)c] = lp_m(p, src[c]) + k[c], ncs[(size_t)c] = lp_ncols(p, src[c]) + k[c];
+        rc = ragged_create(&ch, p->device, n, ms.data(), ncs.data(), 1, p->flags);
+    } else {
+        rc = batch_create(&ch, p->device, n, p->m + k[0], p->ncols + k[0], p->flags, 1, call);
+    }
+    if (rc) return bfail(p, rc, "%s: the child batch: %s", call, g_berr);
+    ch->eps_piv = p->eps_piv;
+    ch->eps_opt = p->eps_opt;
+    if (ragged) {
+        // a parent of one shape records no art_first (lpg_batch_active_columns: ncols), and neither does its child
+        for (int64_t c = 0; c < n; c++) {
+            ch->shape[(size_t)c].nact = (int32_t)(lp_nact(p, src[c]) + k[c]);
+            if (p->ragged) ch->shape[(size_t)c].art_first = p->shape[(size_t)src[c]].art_first + (int32_t)k[c];
+        }
+        if ((rc = push_shapes(ch))) return child_die(p, ch, rc);
+    } else {
+        ch->nact = p->nact + k[0];
+    }
+    *out = ch;
+    return 0;
+}
+
+// The end of lpg_batch_branch and lpg_batch_cut: the jobs to `djobs`, kernel KU (a parent of one shape) or KR
+// (a ragged one) with one workgroup per child, the wait for it. `e`: what the caller's own uploads on the
+// child's stream returned. The child goes to *out, or on an error away.
+template <auto KU, auto KR, class Job, class... Args>
+int grow_finish(lpg_batch **out, lpg_batch *p, lpg_batch *ch, const char *call, hipError_t e, const std::vector<Job> &jobs,
+                const DevBuf &djobs, const Args &...args) {
+    // the parent's stream is idle (every call on it ends with a synchronisation); the copy runs on the child's
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, ch->stream);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)jobs.size()), block(kBlock);
+        if (p->ragged) hipLaunchKernelGGL(KR, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const Job *)djobs.p, args...);
+        else hipLaunchKernelGGL(KU, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const Job *)djobs.p, args...);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
+        return child_die(p, ch, LPG_ERR_DEVICE);
+    }
+    *out = ch;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
+                            lpg_branch_t *out) {
     const char *call = "lpg_batch_branch_select";
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
     if (!mask || !out) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
@@ -1649,17 +1724,16 @@ int branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_m
     if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
     if (rule != LPG_BRANCH_MOST_FRACTIONAL && rule != LPG_BRANCH_FIRST) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
     BHIPCHK(b, hipSetDevice(b->device));
-    // the masks packed at pitch nmask: the kernel reads mask[q * pitch + j - 1] for j <= nmask only
-    const int64_t nrows = ld_mask ? b->count : 1;
     DevBuf dmask, dout;
-    if (hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess ||
-        hipMalloc(&dout.p, (size_t)b->count * sizeof(BranchPick)) != hipSuccess) {
+    int64_t pitch;
+    const hipError_t e = hipMalloc(&dout.p, (size_t)b->count * sizeof(BranchPick)) == hipSuccess
+                             ? stage_mask(dmask, pitch, mask, nmask, ld_mask, b->count, b->stream)
+                             : hipErrorOutOfMemory;
+    if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
         return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and picks of %lld LPs) failed", call, (long long)b->count);
     }
-    BHIPCHK(b, hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask,
-                                (size_t)nrows, hipMemcpyHostToDevice, b->stream));
-    const int64_t pitch = ld_mask ? nmask : 0;
+    BHIPCHK(b, e);
     if (rule == LPG_BRANCH_FIRST)
         hipLaunchKernelGGL(k_batch_branch_select<RULE_BLAND>, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
                            (const uint8_t *)dmask.p, nmask, pitch, int_tol, (BranchPick *)dout.p);
@@ -1672,7 +1746,7 @@ int branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_m
     return 0;
 }
 
-int branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *row, const int8_t *dir) {
+int lpg_batch_branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *row, const int8_t *dir) {
     const char *call = "lpg_batch_branch";
     if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
     *out = nullptr;
@@ -1686,9 +1760,7 @@ int branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const i
     if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
     if (p->nobj == 2) return wrong_kind(p, call);
     for (int64_t c = 0; c < n; c++) {
-        if (src[c] < 0 || src[c] >= p->count)
-            return bfail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c,
-                         (long long)src[c], (long long)(p->count - 1));
+        if (int rc = src_ok(p, call, c, src[c])) return rc;
         const int64_t m = lp_m(p, src[c]), ncols = lp_ncols(p, src[c]);
         if (row[c] < 0 || row[c] >= m)
             return bfail(p, LPG_ERR_ARG, "%s: row[%lld] = %lld outside the rows 0..%lld of LP %lld", call, (long long)c,
@@ -1697,66 +1769,21 @@ int branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const i
             return bfail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + 2 = %lld, ncols + 1 = %lld exceed %d", call,
                          (long long)c, (long long)src[c], (long long)(m + 2), (long long)(ncols + 1), LPG_BATCH_MAX_DIM);
     }
-    // the child batch: the creation of its layout, with the parent's flags
     lpg_batch *ch = nullptr;
-    int rc;
-    if (p->ragged) {
-        std::vector<int64_t> ms((size_t)n), ncs((size_t)n);
-        for (int64_t c = 0; c < n; c++) ms[(size_t)c] = lp_m(p, src[c]) + 1, ncs[(size_t)c] = lp_ncols(p, src[c]) + 1;
-        rc = ragged_create(&ch, p->device, n, ms.data(), ncs.data(), 1, p->flags);
-    } else {
-        rc = batch_create(&ch, p->device, n, p->m + 1, p->ncols + 1, p->flags, 1, call);
-    }
-    if (rc) return bfail(p, rc, "%s: the child batch: %s", call, g_berr);
-    auto die = [&](int code) {
-        snprintf(g_berr, sizeof g_berr, "%s", ch->err);
-        snprintf(p->err, sizeof p->err, "%s", ch->err);
-        lpg_batch_destroy(ch);
-        return code;
-    };
-    ch->eps_piv = p->eps_piv;
-    ch->eps_opt = p->eps_opt;
-    if (p->ragged) {
-        for (int64_t c = 0; c < n; c++) {
-            ch->shape[(size_t)c].nact = p->shape[(size_t)src[c]].nact + 1;
-            ch->shape[(size_t)c].art_first = p->shape[(size_t)src[c]].art_first + 1;
-        }
-        if ((rc = push_shapes(ch))) return die(rc);
-    } else {
-        ch->nact = p->nact + 1;
-    }
+    if (int rc = grow_create(&ch, p, call, n, src, std::vector<int64_t>((size_t)n, 1).data())) return rc;
     std::vector<BranchJob> jobs((size_t)n);
     for (int64_t c = 0; c < n; c++) jobs[(size_t)c] = BranchJob{(int32_t)src[c], (int32_t)row[c], (int32_t)dir[c], 0};
     DevBuf djobs;
     if (hipMalloc(&djobs.p, jobs.size() * sizeof(BranchJob)) != hipSuccess) {
         (void)hipGetLastError();
         bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs) failed", call, (long long)n);
-        return die(LPG_ERR_OOM);
+        return child_die(p, ch, LPG_ERR_OOM);
     }
-    // the parent's stream is idle (every call on it ends with a synchronisation); the copy runs on the child's
-    hipError_t e = hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(BranchJob), hipMemcpyHostToDevice, ch->stream);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)n), block(kBlock);
-        if (p->ragged)
-            hipLaunchKernelGGL(k_batch_branch<true>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch),
-                               (const BranchJob *)djobs.p);
-        else
-            hipLaunchKernelGGL(k_batch_branch<false>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch),
-                               (const BranchJob *)djobs.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bfail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
-        return die(LPG_ERR_DEVICE);
-    }
-    *out = ch;
-    return 0;
+    return grow_finish<k_batch_branch<false>, k_batch_branch<true>>(out, p, ch, call, hipSuccess, jobs, djobs);
 }
 
-int cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int64_t max_cuts,
-               int64_t *ncut, int64_t *rows) {
+int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int64_t max_cuts,
+                         int64_t *ncut, int64_t *rows) {
     const char *call = "lpg_batch_cut_select";
     // what does not depend on the batch first
     if (!mask || !ncut || !rows)
@@ -1768,19 +1795,19 @@ int cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask
     if (b->nobj == 2) return wrong_kind(b, call);
     if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
     BHIPCHK(b, hipSetDevice(b->device));
-    const int64_t nrows = ld_mask ? b->count : 1;
     const size_t nbytes = (size_t)b->count * sizeof(int64_t), rbytes = nbytes * (size_t)max_cuts;
     DevBuf dmask, dncut, drows;
-    if (hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess || hipMalloc(&dncut.p, nbytes) != hipSuccess ||
-        hipMalloc(&drows.p, rbytes) != hipSuccess) {
+    int64_t pitch;
+    const hipError_t e = (hipMalloc(&dncut.p, nbytes) == hipSuccess && hipMalloc(&drows.p, rbytes) == hipSuccess)
+                             ? stage_mask(dmask, pitch, mask, nmask, ld_mask, b->count, b->stream)
+                             : hipErrorOutOfMemory;
+    if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
         return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and rows of %lld LPs) failed", call, (long long)b->count);
     }
-    BHIPCHK(b, hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask,
-                                (size_t)nrows, hipMemcpyHostToDevice, b->stream));
+    BHIPCHK(b, e);
     hipLaunchKernelGGL(k_batch_cut_select, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
-                       (const uint8_t *)dmask.p, nmask, ld_mask ? nmask : (int64_t)0, int_tol, max_cuts, (int64_t *)dncut.p,
-                       (int64_t *)drows.p);
+                       (const uint8_t *)dmask.p, nmask, pitch, int_tol, max_cuts, (int64_t *)dncut.p, (int64_t *)drows.p);
     BHIPCHK(b, hipGetLastError());
     BHIPCHK(b, hipMemcpyAsync(ncut, dncut.p, nbytes, hipMemcpyDeviceToHost, b->stream));
     BHIPCHK(b, hipMemcpyAsync(rows, drows.p, rbytes, hipMemcpyDeviceToHost, b->stream));
@@ -1788,8 +1815,8 @@ int cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask
     return 0;
 }
 
-int cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *first, const int64_t *rows,
-        const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
+int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *first, const int64_t *rows,
+                  const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
     const char *call = "lpg_batch_cut";
     if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
     *out = nullptr;
@@ -1806,13 +1833,11 @@ int cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int6
     if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
     if (p->nobj == 2) return wrong_kind(p, call);
     if (int rc = mask_ok(p, call, nmask, ld_mask)) return rc;
-    bool same_k = true;
+    std::vector<int64_t> ks((size_t)n);
     std::vector<char> seen;
     for (int64_t c = 0; c < n; c++) {
-        const int64_t k = first[c + 1] - first[c];
-        if (src[c] < 0 || src[c] >= p->count)
-            return bfail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c,
-                         (long long)src[c], (long long)(p->count - 1));
+        const int64_t k = ks[(size_t)c] = first[c + 1] - first[c];
+        if (int rc = src_ok(p, call, c, src[c])) return rc;
         if (k > LPG_BATCH_MAX_CUTS)
             return bfail(p, LPG_ERR_ARG, "%s: child %lld has %lld cuts, more than LPG_BATCH_MAX_CUTS = %d", call, (long long)c,
                          (long long)k, LPG_BATCH_MAX_CUTS);
@@ -1831,87 +1856,29 @@ int cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int6
             return bfail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + %lld + 1 = %lld, ncols + %lld = %lld exceed %d", call,
                          (long long)c, (long long)src[c], (long long)k, (long long)(m + k + 1), (long long)k,
                          (long long)(ncols + k), LPG_BATCH_MAX_DIM);
-        same_k &= k == first[1];
     }
-    // the child batch: the creation of its layout, with the parent's flags
-    const bool ragged = p->ragged || !same_k;
     lpg_batch *ch = nullptr;
-    int rc;
-    if (ragged) {
-        std::vector<int64_t> ms((size_t)n), ncs((size_t)n);
-        for (int64_t c = 0; c < n; c++) {
-            const int64_t k = first[c + 1] - first[c];
-            ms[(size_t)c] = lp_m(p, src[c]) + k, ncs[(size_t)c] = lp_ncols(p, src[c]) + k;
-        }
-        rc = ragged_create(&ch, p->device, n, ms.data(), ncs.data(), 1, p->flags);
-    } else {
-        rc = batch_create(&ch, p->device, n, p->m + first[1], p->ncols + first[1], p->flags, 1, call);
-    }
-    if (rc) return bfail(p, rc, "%s: the child batch: %s", call, g_berr);
-    auto die = [&](int code) {
-        snprintf(g_berr, sizeof g_berr, "%s", ch->err);
-        snprintf(p->err, sizeof p->err, "%s", ch->err);
-        lpg_batch_destroy(ch);
-        return code;
-    };
-    ch->eps_piv = p->eps_piv;
-    ch->eps_opt = p->eps_opt;
-    if (ragged) {
-        // a parent of one shape records no art_first (lpg_batch_active_columns: ncols), and neither does its child
-        for (int64_t c = 0; c < n; c++) {
-            const int64_t k = first[c + 1] - first[c];
-            ch->shape[(size_t)c].nact = (int32_t)(lp_nact(p, src[c]) + k);
-            if (p->ragged) ch->shape[(size_t)c].art_first = p->shape[(size_t)src[c]].art_first + (int32_t)k;
-        }
-        if ((rc = push_shapes(ch))) return die(rc);
-    } else {
-        ch->nact = p->nact + first[1];
-    }
+    if (int rc = grow_create(&ch, p, call, n, src, ks.data())) return rc;
     std::vector<CutJob> jobs((size_t)n);
     std::vector<int32_t> rows32((size_t)first[n]);
-    for (int64_t c = 0; c < n; c++)
-        jobs[(size_t)c] = CutJob{(int32_t)src[c], (int32_t)first[c], (int32_t)(first[c + 1] - first[c]), 0};
+    for (int64_t c = 0; c < n; c++) jobs[(size_t)c] = CutJob{(int32_t)src[c], (int32_t)first[c], (int32_t)ks[(size_t)c], 0};
     for (int64_t t = 0; t < first[n]; t++) rows32[(size_t)t] = (int32_t)rows[t];
-    const int64_t nrows = ld_mask ? p->count : 1;
     DevBuf djobs, drows, dmask;
-    if (hipMalloc(&djobs.p, jobs.size() * sizeof(CutJob)) != hipSuccess ||
-        hipMalloc(&drows.p, rows32.size() * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&dmask.p, (size_t)(nrows * nmask)) != hipSuccess) {
+    int64_t pitch;
+    hipError_t e = (hipMalloc(&djobs.p, jobs.size() * sizeof(CutJob)) == hipSuccess &&
+                    hipMalloc(&drows.p, rows32.size() * sizeof(int32_t)) == hipSuccess)
+                       ? stage_mask(dmask, pitch, mask, nmask, ld_mask, p->count, ch->stream)
+                       : hipErrorOutOfMemory;
+    if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
         bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, %lld rows, masks) failed", call, (long long)n, (long long)first[n]);
-        return die(LPG_ERR_OOM);
+        return child_die(p, ch, LPG_ERR_OOM);
     }
-    // the parent's stream is idle (every call on it ends with a synchronisation); the copy runs on the child's
-    hipError_t e = hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(CutJob), hipMemcpyHostToDevice, ch->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(drows.p, rows32.data(), rows32.size() * sizeof(int32_t), hipMemcpyHostToDevice, ch->stream);
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(dmask.p, (size_t)nmask, mask, (size_t)(ld_mask ? ld_mask : nmask), (size_t)nmask, (size_t)nrows,
-                             hipMemcpyHostToDevice, ch->stream);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)n), block(kBlock);
-        const int64_t pitch = ld_mask ? nmask : 0;
-        if (p->ragged)
-            hipLaunchKernelGGL(k_batch_cut<true>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const CutJob *)djobs.p,
-                               (const int32_t *)drows.p, (const uint8_t *)dmask.p, nmask, pitch);
-        else
-            hipLaunchKernelGGL(k_batch_cut<false>, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const CutJob *)djobs.p,
-                               (const int32_t *)drows.p, (const uint8_t *)dmask.p, nmask, pitch);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bfail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
-        return die(LPG_ERR_DEVICE);
-    }
-    *out = ch;
-    return 0;
+    return grow_finish<k_batch_cut<false>, k_batch_cut<true>>(out, p, ch, call, e, jobs, djobs, (const int32_t *)drows.p,
+                                                              (const uint8_t *)dmask.p, nmask, pitch);
 }
-
-}  // namespace
-
-extern "C" {
 
 const char *lpg_batch_last_error(const lpg_batch *b) { return b ? b->err : g_berr; }
 
@@ -2055,12 +2022,12 @@ int lpg_batch_set_objective_packed(lpg_batch *b, const double *cost) {
 
 int lpg_batch_solve_two_phase_ragged(lpg_batch *b, const int64_t *art_first, const double *cost, int64_t max_pivots,
                                      int rule, lpg_result *out) {
-    return solve_artificial_ragged(b, M_TWO_PHASE, "lpg_batch_solve_two_phase_ragged", art_first, cost, max_pivots, rule, out);
+    return solve_artificial(b, M_TWO_PHASE, "lpg_batch_solve_two_phase_ragged", true, art_first, cost, 0, max_pivots, rule, out);
 }
 
 int lpg_batch_solve_big_m_ragged(lpg_batch *b, const int64_t *art_first, const double *cost, int64_t max_pivots, int rule,
                                  lpg_result *out) {
-    return solve_artificial_ragged(b, M_BIG_M, "lpg_batch_solve_big_m_ragged", art_first, cost, max_pivots, rule, out);
+    return solve_artificial(b, M_BIG_M, "lpg_batch_solve_big_m_ragged", true, art_first, cost, 0, max_pivots, rule, out);
 }
 
 int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, int64_t ld, const int64_t *basis) {
@@ -2142,12 +2109,12 @@ int lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out) {
 
 int lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
                               int rule, lpg_result *out) {
-    return solve_artificial(b, M_TWO_PHASE, "lpg_batch_solve_two_phase", art_first, cost, ld_cost, max_pivots, rule, out);
+    return solve_artificial(b, M_TWO_PHASE, "lpg_batch_solve_two_phase", false, &art_first, cost, ld_cost, max_pivots, rule, out);
 }
 
 int lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost, int64_t max_pivots,
                           int rule, lpg_result *out) {
-    return solve_artificial(b, M_BIG_M, "lpg_batch_solve_big_m", art_first, cost, ld_cost, max_pivots, rule, out);
+    return solve_artificial(b, M_BIG_M, "lpg_batch_solve_big_m", false, &art_first, cost, ld_cost, max_pivots, rule, out);
 }
 
 int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
@@ -2233,26 +2200,6 @@ int lpg_batch_active_columns(const lpg_batch *cb, int64_t lp, int64_t *nact, int
     if (nact) *nact = lp_nact(b, lp);
     if (art_first) *art_first = b->ragged ? b->shape[(size_t)lp].art_first : b->ncols;
     return 0;
-}
-
-int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
-                            lpg_branch_t *out) {
-    return branch_select(b, mask, nmask, ld_mask, int_tol, rule, out);
-}
-
-int lpg_batch_branch(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *row,
-                     const int8_t *dir) {
-    return branch(child, parent, n, src, row, dir);
-}
-
-int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int64_t max_cuts,
-                         int64_t *ncut, int64_t *rows) {
-    return cut_select(b, mask, nmask, ld_mask, int_tol, max_cuts, ncut, rows);
-}
-
-int lpg_batch_cut(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src, const int64_t *first,
-                  const int64_t *rows, const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
-    return cut(child, parent, n, src, first, rows, mask, nmask, ld_mask);
 }
 
 }  // extern "C"

@@ -465,13 +465,9 @@ class BatchEngine:
         """The branching row of every LP (include/lpg.h lpg_batch_branch_select). mask: [nmask] (the same for
         every LP) or [count, nmask], non-zero where tableau column 1 + index is integer-constrained. Returns
         (row, col, value), one entry per LP; row = col = -1 where every integer column is integral."""
-        mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-        if mk.ndim not in (1, 2) or (mk.ndim == 2 and mk.shape[0] != self.count):
-            raise LPGError(f"branch_select: mask of shape {mk.shape}, want [nmask] or [{self.count}, nmask]")
+        mk, mp, nmask, ld = self._mask(mask, "branch_select")
         out = (L.Branch * self.count)()
-        self._check(self.lib.lpg_batch_branch_select(self._b, mk.ctypes.data_as(L.c_uint8_p), mk.shape[-1],
-                                                     mk.shape[1] if mk.ndim == 2 else 0, int_tol, rule, out),
-                    "lpg_batch_branch_select")
+        self._check(self.lib.lpg_batch_branch_select(self._b, mp, nmask, ld, int_tol, rule, out), "lpg_batch_branch_select")
         a = np.frombuffer(out, dtype=np.dtype([("row", np.int64), ("col", np.int64), ("value", np.float64)]))
         return a["row"].copy(), a["col"].copy(), a["value"].copy()
 
@@ -488,10 +484,18 @@ class BatchEngine:
         self._check(self.lib.lpg_batch_branch(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
                                               row.ctypes.data_as(L.c_int64_p), d.ctypes.data_as(L.c_int8_p)),
                     "lpg_batch_branch")
-        return self._child(child, src)
+        return self._wrap_child(child, src, [1] * len(src))
 
-    def _child(self, handle, src):
-        return BatchEngine(len(src), self.m + 1, self.ncols + 1, lib=self.lib, _handle=handle)
+    def _wrap_child(self, handle, src, grow):
+        """The engine that owns the child batch `handle` of branch() or cut(): child c is LP src[c] with grow[c]
+        more rows and columns; a RaggedBatchEngine where the library made a ragged batch (lpg_batch_info)."""
+        info = L.BatchInfo()
+        self.lib.lpg_batch_info(handle, ctypes.byref(info))
+        if info.pad:
+            shapes = [(self._shape_of(q)[0] + k, self._shape_of(q)[1] + k) for q, k in zip(src, grow)]
+            return RaggedBatchEngine(shapes, lib=self.lib, _handle=handle)
+        (m, ncols), k = self._shape_of(src[0]), grow[0]   # one shape: every child's
+        return BatchEngine(len(src), m + k, ncols + k, lib=self.lib, _handle=handle)
 
     # -- cuts ------------------------------------------------------------
     def _mask(self, mask, what):
@@ -531,12 +535,7 @@ class BatchEngine:
         self._check(self.lib.lpg_batch_cut(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
                                            first.ctypes.data_as(L.c_int64_p), rows.ctypes.data_as(L.c_int64_p), mp, nmask, ld),
                     "lpg_batch_cut")
-        info = L.BatchInfo()
-        self.lib.lpg_batch_info(child, ctypes.byref(info))
-        shapes = [(self._shape_of(q)[0] + len(r), self._shape_of(q)[1] + len(r)) for q, r in zip(src, per)]
-        if info.pad:                                      # lpg_batch_info: a ragged batch
-            return RaggedBatchEngine(shapes, lib=self.lib, _handle=child)
-        return BatchEngine(len(src), shapes[0][0], shapes[0][1], lib=self.lib, _handle=child)
+        return self._wrap_child(child, src, [len(r) for r in per])
 
     def _shape_of(self, q):
         return self.m, self.ncols
@@ -566,9 +565,6 @@ class RaggedBatchEngine(BatchEngine):
             if rc != 0:
                 raise LPGError(f"lpg_batch_create_ragged rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
         self.m, self.ncols = int(ms.max()), int(ncs.max())
-
-    def _child(self, handle, src):
-        return RaggedBatchEngine([(self.shapes[q][0] + 1, self.shapes[q][1] + 1) for q in src], lib=self.lib, _handle=handle)
 
     def _shape_of(self, q):
         return self.shapes[q]

@@ -152,6 +152,76 @@ def test_a_cut_on_a_branched_child_counts_the_branch_slack_as_continuous(kind, m
 
 
 # ---------------------------------------------------------------------------
+# one cut against one bound: the two calls share the copy that makes a child
+# ---------------------------------------------------------------------------
+def _solved(m, n, B=3):
+    import linearprogramming_amd as lpg
+    e = lpg.BatchEngine(B, m, n + m + 1)
+    e.generate(n, bc.SEED, 0)
+    assert all(r.status == br.OPTIMAL for r in e.solve(br.BUDGET))
+    return e
+
+
+def _same_outside_the_new_row(parent, shapes, nacts):
+    """A child by cut() with one cut and the two children by branch() on the same row of every LP of `parent`
+    (LP q of shape shapes[q] = (m, ncols) with nacts[q] active columns): bit for bit the same in rows 0..m-1, the
+    objective row and the basis, and in the new row the same 1 in the new slack column nact + 1."""
+    B = len(shapes)
+    ones = np.ones(max(nc for _, nc in shapes) - 1, dtype=np.uint8)
+    row = parent.branch_select(ones)[0]
+    assert (row >= 0).all()                                 # every LP of these has a fractional basic variable
+    src = np.arange(B)
+    cut = parent.cut(src, [[r] for r in row], ones)
+    bound = parent.branch(np.repeat(src, 2), np.repeat(row, 2), np.tile([-1, 1], B))
+    try:
+        assert type(cut) is type(bound) is type(parent)
+        cT, cB, bT, bB = list(cut.get_rows()), list(cut.get_basis()), list(bound.get_rows()), list(bound.get_basis())
+        for q, ((m, nc), nact) in enumerate(zip(shapes, nacts)):
+            assert cT[q].shape == (m + 2, nc + 1) and cut.active_columns(q)[0] == nact + 1
+            keep = np.arange(m + 2) != m
+            assert (cT[q][keep, nact + 1] == 0.0).all() and cT[q][m, nact + 1] == 1.0 and cB[q][m] == nact + 1
+            for child in (2 * q, 2 * q + 1):
+                assert bT[child].shape == cT[q].shape and bound.active_columns(child) == cut.active_columns(q)
+                assert np.array_equal(bc.bits(bT[child][keep]), bc.bits(cT[q][keep])), (q, child)
+                assert bT[child][m, nact + 1] == 1.0
+                assert np.array_equal(bB[child], cB[q]), (q, child)
+    finally:
+        cut.close()
+        bound.close()
+
+
+@pytest.mark.parametrize("inert", [0, 1])
+@pytest.mark.parametrize("m,n", [(5, 6), (8, 8)])
+def test_one_cut_and_a_bound_on_the_same_row_differ_in_the_new_row_only(m, n, inert):
+    """nact + 1 is even at (5, 6) and odd at (8, 8) (all of columns 0..nact as pairs, or one of them in the tail);
+    `inert` columns behind nact are the shifted part, which turns that parity round, and some of them are basic."""
+    nc = n + m + 1
+    e = _solved(m, n)
+    try:
+        if inert:
+            e.set_active_columns(nc - 1 - inert)
+            assert (e.get_basis() > nc - 1 - inert).any()   # the basis shift
+        _same_outside_the_new_row(e, [(m, nc)] * e.count, [nc - 1 - inert] * e.count)
+    finally:
+        e.close()
+
+
+def test_one_cut_and_a_bound_on_the_same_row_of_a_ragged_parent():
+    import linearprogramming_amd as lpg
+    shapes = [(5, 12), (8, 17), (5, 12)]
+    g = lpg.BatchEngine.ragged(shapes)
+    a, b = _solved(5, 6), _solved(8, 8)
+    try:
+        Ta, Ba, Tb, Bb = a.get_rows(), a.get_basis(), b.get_rows(), b.get_basis()
+        g.load([Ta[0], Tb[0], Ta[1]], [Ba[0], Bb[0], Ba[1]])
+        assert all(r.status == br.OPTIMAL and r.pivots == 0 for r in g.solve(br.BUDGET))
+        _same_outside_the_new_row(g, shapes, [nc - 1 for _, nc in shapes])
+    finally:
+        for x in (g, a, b):
+            x.close()
+
+
+# ---------------------------------------------------------------------------
 # selection
 # ---------------------------------------------------------------------------
 def test_cut_select_equals_numpy_for_every_max_cuts_and_a_mask_per_lp():

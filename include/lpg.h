@@ -625,6 +625,58 @@ int  lpg_batch_cut(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_
                    const int64_t *first /* n + 1 offsets into rows */, const int64_t *rows,
                    const uint8_t *mask, int64_t nmask, int64_t ld_mask);
 
+/* ---- scenarios: the same LPs under other right-hand sides ----
+ *
+ * For parameter sweeps and scenario sets: LPs that differ only in b. A solved
+ * tableau carries B^-1 in the columns that were the identity when the LP was
+ * stated, so for a new right-hand side b' column 0 is B^-1 b'; the objective
+ * row's entries d_j do not change, the LP stays dual feasible, and
+ * lpg_batch_solve_dual re-optimises it in a few pivots where a cold solve
+ * would start from the slack or artificial basis again. No tableau crosses
+ * the host. Both calls work on batches of one shape and on ragged ones and
+ * refuse a Big-M batch (LPG_ERR_STATE).
+ *
+ * `ident` states the frame the right-hand sides are given in: ident[i] of LP
+ * q is the column (1..N_q) that was the unit vector e_i in that frame; for a
+ * loaded LP the basis it was loaded with, for the generators the slack or
+ * artificial column of row i. It is laid out like the bases: m entries per LP,
+ * count x m for a batch of one shape, packed as lpg_batch_get_basis_packed's
+ * for a ragged one. For every row r = 0..m of the LP, the objective row
+ * included:
+ *     acc = 0.0; for i = 0..m-1: acc = acc + T[r][ident[i]] * rhs[i]
+ *     T[r][0] = acc
+ * i ascending, the product and the sum one rounding each (nothing contracted
+ * into an fma), so a host restatement reproduces every bit
+ * (tests/scenario_cases.py). The objective row's column 0 is the objective of
+ * the new basic solution only where the ident columns cost 0: slacks do, and
+ * so do artificials in phase II; otherwise follow with lpg_batch_set_objective.
+ * Nothing checks that an LP was LPG_OPTIMAL: lpg_batch_solve_dual refuses an
+ * LP that is not dual feasible. A lane per row gathers the row's entries;
+ * LPG_SCENARIO_WALK=tile reads them tile by tile through LDS instead, which
+ * was measured and is slower at the shapes tried; the bits are the same. */
+/* *child = a new batch of n LPs: child c is LP src[c] of `parent` unchanged
+ * (shape, basis, active columns, a ragged parent's art_first, the inert
+ * artificial columns behind nact, which are the B^-1 of their rows) except for
+ * column 0, restated for rhs: packed, child c's m_src[c] values behind child
+ * c-1's; ident is the parent's. The child inherits tolerances and flags; its
+ * LPs are fresh: LPG_RUNNING, no pivots, empty log. A parent of one shape gives
+ * a child of one shape, a ragged parent a ragged child. The parent is
+ * unchanged. One launch (k_batch_scenario, one workgroup per child) copies
+ * the parent and computes the column. Before any device work, with a message
+ * that names the call and the first offending index: `child` NULL, n < 1, NULL
+ * src / ident / rhs, NULL parent (LPG_ERR_ARG, in this order, none of them
+ * looks at the parent); then a Big-M parent (LPG_ERR_STATE), a src outside the
+ * parent, an ident entry outside 1..N_q, a rhs entry that is not finite
+ * (LPG_ERR_ARG). On any error *child is NULL. */
+int  lpg_batch_scenario(lpg_batch **child, lpg_batch *parent, int64_t n, const int64_t *src,
+                        const int64_t *ident, const double *rhs);
+/* The same column on every LP of `b`, in place (k_batch_set_rhs): ident is
+ * the batch's own, rhs holds LP q's m_q values, LP after LP. Column 0 is only
+ * written and the other columns only read. The LPs start again as after
+ * lpg_batch_load; B^-1 survives any number of dual pivots, so a sweep in steps
+ * needs no new batch. Refusals as lpg_batch_scenario's. */
+int  lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs);
+
 #ifdef __cplusplus
 }
 #endif

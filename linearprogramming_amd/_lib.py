@@ -170,6 +170,9 @@ PROTOTYPES = [
                                             ctypes.c_int64, c_int64_p, c_int64_p]),
     ("lpg_batch_cut", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64, c_int64_p, c_int64_p,
                                      c_int64_p, c_uint8_p, ctypes.c_int64, ctypes.c_int64]),
+    ("lpg_batch_scenario", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64, c_int64_p,
+                                          c_int64_p, c_double_p]),
+    ("lpg_batch_set_rhs", ctypes.c_int, [ctypes.c_void_p, c_int64_p, c_double_p]),
 ]
 
 

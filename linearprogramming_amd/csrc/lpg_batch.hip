@@ -55,6 +55,11 @@
 // grow_create makes the child batch and grow_finish launches the copy; what
 // lpg_batch_branch and lpg_batch_cut keep is their own argument checks and
 // job arrays.
+//
+// Scenarios (lpg_batch_scenario, lpg_batch_set_rhs): the same LPs under other
+// right-hand sides. k_batch_scenario is grow_copy by no row plus
+// scenario_column, which restates column 0 from the columns that hold B^-1;
+// k_batch_set_rhs is scenario_column in place.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -1011,6 +1016,102 @@ __global__ __launch_bounds__(kBlock) void k_batch_cut(BatchGeo p, BatchGeo c, co
     });
 }
 
+// ------------------------------------------------------------------------
+// scenarios (include/lpg.h, "scenarios"): the same LP under another
+// right-hand side. The columns that were the identity when the LP was stated
+// (`ident`) hold B^-1 now, so column 0 of every row r, the objective row
+// included, is
+//     acc = 0.0; for i = 0..m-1: acc = acc + T[r][ident[i]] * rhs[i]
+// in that order, every operation one rounding (the product spelled
+// __dmul_rn, as the cut's), so tests/scenario_cases.py reproduces every bit.
+// ------------------------------------------------------------------------
+
+struct ScenarioJob {          // child c of lpg_batch_scenario: validated on the host
+    int32_t src, pad;
+    int64_t rhs_off;          // its right-hand side at rhs[rhs_off .. rhs_off + m_src)
+};
+
+constexpr int WALK_TILE = 0, WALK_ROWS = 1;   // how scenario_column walks the tableau
+constexpr int kScnRows = 64, kScnCols = 32;   // WALK_TILE: rows and ident columns of a tile
+
+// LP's m ident columns and right-hand side into the launch's dynamic LDS: [rhs: m doubles][ident: m int32]
+__device__ __forceinline__ void scenario_stage(const int64_t *ident, const double *rhs, int64_t m, double *&sR, int32_t *&sI) {
+    extern __shared__ double smem[];
+    sR = smem;
+    sI = (int32_t *)(smem + m);
+    for (int64_t i = threadIdx.x; i < m; i += kBlock) {
+        sR[i] = rhs[i];
+        sI[i] = (int32_t)ident[i];
+    }
+    __syncthreads();
+}
+
+// out[r * old] = sum_i T[r][sI[i]] * sR[i] for the rows r = 0..m of the tableau T (pitch ld), the additions of
+// a row in ascending i. T's column 0 is not read, so out may be it. WALK_ROWS: a lane owns a row and gathers
+// its m entries from device memory, lanes a pitch apart. WALK_TILE: the workgroup reads kScnRows x kScnCols
+// entries at a time along the rows (ident columns are mostly neighbours: slacks, artificials) into an LDS
+// tile of odd pitch; then lane = row adds its kScnCols products in order, the sum kept in its register from
+// tile to tile of the row block.
+__device__ __forceinline__ void scenario_column(const double *T, int64_t ld, int64_t m, const int32_t *sI, const double *sR,
+                                                double *out, int64_t old, int walk) {
+    const int tid = threadIdx.x;
+    if (walk == WALK_ROWS) {
+        for (int64_t r = tid; r <= m; r += kBlock) {
+            const double *row = T + r * ld;
+            double acc = 0.0;
+#pragma unroll 4
+            for (int64_t i = 0; i < m; i++) acc = acc + __dmul_rn(row[sI[i]], sR[i]);
+            out[r * old] = acc;
+        }
+        return;
+    }
+    __shared__ double tile[kScnRows][kScnCols + 1];
+    const int ti = tid & (kScnCols - 1), tr0 = tid / kScnCols;     // a lane's column of the tile, its first row
+    for (int64_t r0 = 0; r0 <= m; r0 += kScnRows) {
+        double acc = 0.0;
+        for (int64_t i0 = 0; i0 < m; i0 += kScnCols) {
+            const int64_t nc = m - i0 < kScnCols ? m - i0 : kScnCols;
+            if (ti < nc) {
+                const int64_t col = sI[i0 + ti];
+                for (int tr = tr0; tr < kScnRows && r0 + tr <= m; tr += kBlock / kScnCols)
+                    tile[tr][ti] = T[(r0 + tr) * ld + col];
+            }
+            __syncthreads();
+            if (tid < kScnRows && r0 + tid <= m)
+                for (int64_t i = 0; i < nc; i++) acc = acc + __dmul_rn(tile[tid][i], sR[i0 + i]);
+            __syncthreads();
+        }
+        if (tid < kScnRows && r0 + tid <= m) out[(r0 + tid) * old] = acc;
+    }
+}
+
+// Child blockIdx.x of `c` from LP job.src of `p` (RG: both ragged, as the parent is): grow_copy by no row, so
+// the child is the parent moved as 16-byte pairs, inert artificial columns included; then column 0 from the
+// parent's tableau. The copy writes the child's column 0 as well, from other lanes: the barrier puts
+// scenario_column's stores behind it.
+template <bool RG>
+__global__ __launch_bounds__(kBlock) void k_batch_scenario(BatchGeo p, BatchGeo c, const ScenarioJob *jobs, const int64_t *ident,
+                                                           const double *rhs, int walk) {
+    const ScenarioJob job = jobs[blockIdx.x];
+    const LpGeo ps = lp_geo<RG>(p, job.src, 1, 0), cs = lp_geo<RG>(c, blockIdx.x, 1, 0);
+    double *sR;
+    int32_t *sI;
+    scenario_stage(ident + ps.b_off, rhs + job.rhs_off, ps.m, sR, sI);
+    grow_copy(p, ps, c, cs, 0, [](int64_t) { return 0; }, [](int64_t) { return [](double x, int64_t) { return x; }; });
+    __syncthreads();
+    scenario_column(p.T + ps.t_off, ps.ld, ps.m, sI, sR, c.T + cs.t_off, cs.ld, walk);
+}
+
+// LP blockIdx.x of `g` restated in place: column 0 is only written, the columns from 1 on only read
+__global__ __launch_bounds__(kBlock) void k_batch_set_rhs(BatchGeo g, const int64_t *ident, const double *rhs, int walk) {
+    const LpGeo s = lp_geo_any(g, blockIdx.x);
+    double *sR;
+    int32_t *sI;
+    scenario_stage(ident + s.b_off, rhs + s.b_off, s.m, sR, sI);
+    double *T = g.T + s.t_off;
+    scenario_column(T, s.ld, s.m, sI, sR, T, s.ld, walk);
+}
+
 }  // namespace lpg
 
 // ---------------------------------------------------------------------------
@@ -1152,19 +1253,26 @@ int alloc_log(lpg_batch *b, int64_t cap) {
 // which solver a call runs
 enum Method { M_PRIMAL, M_DUAL, M_TWO_PHASE, M_BIG_M };
 
+// the dynamic LDS limit of kernel K (`name` for the error message) raised to `bytes`, once per device
+template <auto K>
+int raise_lds(lpg_batch *b, const char *name, int bytes = kBatchMaxLds) {
+    static std::atomic<unsigned long long> attr{0};
+    const int dev = b->device & 63;
+    if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
+        if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(%s, %d bytes of LDS) failed", name, bytes);
+        }
+        attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
+    }
+    return 0;
+}
+
 // one launch of solve kernel K (`name` for the error message) on group `gr`,
 // one workgroup per LP; its dynamic LDS limit is raised once per device
 template <auto K, class... Args>
 int launch_lp(lpg_batch *b, const lpg_batch::Group &gr, const char *name, const Args &...args) {
-    static std::atomic<unsigned long long> attr{0};
-    const int dev = b->device & 63;
-    if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, kBatchMaxLds) != hipSuccess) {
-            (void)hipGetLastError();
-            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(%s, %d bytes of LDS) failed", name, kBatchMaxLds);
-        }
-        attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
-    }
+    if (int rc = raise_lds<K>(b, name)) return rc;
     hipLaunchKernelGGL(K, dim3((unsigned)gr.count), dim3(kBlock), (size_t)gr.lds, b->stream, bgeo(b, gr), args...);
     return 0;
 }
@@ -1686,18 +1794,18 @@ int grow_create(lpg_batch **out, lpg_batch *p, const char *call, int64_t n, cons
 }
 
 // The end of lpg_batch_branch and lpg_batch_cut: the jobs to `djobs`, kernel KU (a parent of one shape) or KR
-// (a ragged one) with one workgroup per child, the wait for it. `e`: what the caller's own uploads on the
-// child's stream returned. The child goes to *out, or on an error away.
+// (a ragged one) with one workgroup per child and `lds` bytes of dynamic LDS, the wait for it. `e`: what the
+// caller's own uploads on the child's stream returned. The child goes to *out, or on an error away.
 template <auto KU, auto KR, class Job, class... Args>
 int grow_finish(lpg_batch **out, lpg_batch *p, lpg_batch *ch, const char *call, hipError_t e, const std::vector<Job> &jobs,
-                const DevBuf &djobs, const Args &...args) {
+                const DevBuf &djobs, size_t lds, const Args &...args) {
     // the parent's stream is idle (every call on it ends with a synchronisation); the copy runs on the child's
     if (e == hipSuccess)
         e = hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, ch->stream);
     if (e == hipSuccess) {
         const dim3 grid((unsigned)jobs.size()), block(kBlock);
-        if (p->ragged) hipLaunchKernelGGL(KR, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const Job *)djobs.p, args...);
-        else hipLaunchKernelGGL(KU, grid, block, 0, ch->stream, bgeo(p), bgeo(ch), (const Job *)djobs.p, args...);
+        if (p->ragged) hipLaunchKernelGGL(KR, grid, block, lds, ch->stream, bgeo(p), bgeo(ch), (const Job *)djobs.p, args...);
+        else hipLaunchKernelGGL(KU, grid, block, lds, ch->stream, bgeo(p), bgeo(ch), (const Job *)djobs.p, args...);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
@@ -1710,9 +1818,105 @@ int grow_finish(lpg_batch **out, lpg_batch *p, lpg_batch *ch, const char *call, 
     return 0;
 }
 
+// how scenario_column walks the tableau: a lane per row, the faster of the two where measured (DESIGN.md §3.7,
+// "Scenarios"); LPG_SCENARIO_WALK=tile: the tiled walk
+int scenario_walk() { return env_is("LPG_SCENARIO_WALK", "tile") ? WALK_TILE : WALK_ROWS; }
+
+// dynamic LDS of a scenario workgroup: the right-hand side and the ident columns of an LP of m rows
+// (scenario_stage), and the most of it (beside the static tile of scenario_column it stays under the CU's LDS)
+size_t scenario_lds(int64_t m) { return (size_t)m * (sizeof(double) + sizeof(int32_t)); }
+constexpr int kScenarioMaxLds = LPG_BATCH_MAX_DIM * (int)(sizeof(double) + sizeof(int32_t));
+
+// every ident entry of every LP of `b` names one of its columns 1..N
+int ident_ok(lpg_batch *b, const char *call, const int64_t *ident) {
+    for (int64_t q = 0, at = 0; q < b->count; q++)
+        for (int64_t i = 0, m = lp_m(b, q), N = lp_ncols(b, q) - 1; i < m; i++, at++)
+            if (ident[at] < 1 || ident[at] > N)
+                return bfail(b, LPG_ERR_ARG, "%s: ident[%lld] = %lld (row %lld of LP %lld) outside the columns 1..%lld", call,
+                             (long long)at, (long long)ident[at], (long long)i, (long long)q, (long long)N);
+    return 0;
+}
+
+// rhs[at .. at + m) is finite; `whose` names the LP or child it belongs to
+int rhs_ok(lpg_batch *b, const char *call, const double *rhs, int64_t at, int64_t m, const char *whose, int64_t q) {
+    for (int64_t i = 0; i < m; i++)
+        if (!std::isfinite(rhs[at + i]))
+            return bfail(b, LPG_ERR_ARG, "%s: rhs[%lld] = %g (row %lld of %s %lld) is not finite", call, (long long)(at + i),
+                         rhs[at + i], (long long)i, whose, (long long)q);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int lpg_batch_scenario(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *ident, const double *rhs) {
+    const char *call = "lpg_batch_scenario";
+    if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
+    *out = nullptr;
+    // what does not depend on the parent first
+    if (n < 1) return bfail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
+    if (!src || !ident || !rhs)
+        return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !ident ? "ident" : "rhs");
+    if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
+    if (p->nobj == 2) return wrong_kind(p, call);
+    for (int64_t c = 0; c < n; c++)
+        if (int rc = src_ok(p, call, c, src[c])) return rc;
+    if (int rc = ident_ok(p, call, ident)) return rc;
+    std::vector<ScenarioJob> jobs((size_t)n);
+    int64_t at = 0;
+    for (int64_t c = 0; c < n; c++) {
+        const int64_t m = lp_m(p, src[c]);
+        if (int rc = rhs_ok(p, call, rhs, at, m, "child", c)) return rc;
+        jobs[(size_t)c] = ScenarioJob{(int32_t)src[c], 0, at};
+        at += m;
+    }
+    lpg_batch *ch = nullptr;
+    if (int rc = grow_create(&ch, p, call, n, src, std::vector<int64_t>((size_t)n, 0).data())) return rc;
+    if (int rc = p->ragged ? raise_lds<k_batch_scenario<true>>(ch, "k_batch_scenario", kScenarioMaxLds)
+                           : raise_lds<k_batch_scenario<false>>(ch, "k_batch_scenario", kScenarioMaxLds))
+        return child_die(p, ch, rc);
+    DevBuf djobs, dident, drhs;
+    const size_t ibytes = (size_t)p->b_total * sizeof(int64_t), rbytes = (size_t)at * sizeof(double);
+    if (hipMalloc(&djobs.p, jobs.size() * sizeof(ScenarioJob)) != hipSuccess || hipMalloc(&dident.p, ibytes) != hipSuccess ||
+        hipMalloc(&drhs.p, rbytes) != hipSuccess) {
+        (void)hipGetLastError();
+        bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, ident, %lld right-hand sides) failed", call, (long long)n, (long long)at);
+        return child_die(p, ch, LPG_ERR_OOM);
+    }
+    hipError_t e = hipMemcpyAsync(dident.p, ident, ibytes, hipMemcpyHostToDevice, ch->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(drhs.p, rhs, rbytes, hipMemcpyHostToDevice, ch->stream);
+    return grow_finish<k_batch_scenario<false>, k_batch_scenario<true>>(out, p, ch, call, e, jobs, djobs, scenario_lds(p->m),
+                                                                        (const int64_t *)dident.p, (const double *)drhs.p,
+                                                                        scenario_walk());
+}
+
+int lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs) {
+    const char *call = "lpg_batch_set_rhs";
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (!ident || !rhs) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !ident ? "ident" : "rhs");
+    if (b->nobj == 2) return wrong_kind(b, call);
+    if (int rc = ident_ok(b, call, ident)) return rc;
+    for (int64_t q = 0, at = 0; q < b->count; at += lp_m(b, q), q++)
+        if (int rc = rhs_ok(b, call, rhs, at, lp_m(b, q), "LP", q)) return rc;
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = raise_lds<k_batch_set_rhs>(b, "k_batch_set_rhs", kScenarioMaxLds)) return rc;
+    DevBuf dident, drhs;
+    if (hipMalloc(&dident.p, (size_t)b->b_total * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc(&drhs.p, (size_t)b->b_total * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(ident and right-hand sides of %lld LPs) failed", call, (long long)b->count);
+    }
+    BHIPCHK(b, hipMemcpyAsync(dident.p, ident, (size_t)b->b_total * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
+    BHIPCHK(b, hipMemcpyAsync(drhs.p, rhs, (size_t)b->b_total * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    hipLaunchKernelGGL(k_batch_set_rhs, dim3((unsigned)b->count), dim3(kBlock), scenario_lds(b->m), b->stream, bgeo(b),
+                       (const int64_t *)dident.p, (const double *)drhs.p, scenario_walk());
+    hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
+    BHIPCHK(b, hipGetLastError());
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    b->pivoted = false;
+    return 0;
+}
 
 int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
                             lpg_branch_t *out) {
@@ -1779,7 +1983,7 @@ int lpg_batch_branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *sr
         bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs) failed", call, (long long)n);
         return child_die(p, ch, LPG_ERR_OOM);
     }
-    return grow_finish<k_batch_branch<false>, k_batch_branch<true>>(out, p, ch, call, hipSuccess, jobs, djobs);
+    return grow_finish<k_batch_branch<false>, k_batch_branch<true>>(out, p, ch, call, hipSuccess, jobs, djobs, 0);
 }
 
 int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int64_t max_cuts,
@@ -1876,7 +2080,7 @@ int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, 
     }
     if (e == hipSuccess)
         e = hipMemcpyAsync(drows.p, rows32.data(), rows32.size() * sizeof(int32_t), hipMemcpyHostToDevice, ch->stream);
-    return grow_finish<k_batch_cut<false>, k_batch_cut<true>>(out, p, ch, call, e, jobs, djobs, (const int32_t *)drows.p,
+    return grow_finish<k_batch_cut<false>, k_batch_cut<true>>(out, p, ch, call, e, jobs, djobs, 0, (const int32_t *)drows.p,
                                                               (const uint8_t *)dmask.p, nmask, pitch);
 }
 

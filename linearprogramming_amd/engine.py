@@ -537,6 +537,45 @@ class BatchEngine:
                     "lpg_batch_cut")
         return self._wrap_child(child, src, [len(r) for r in per])
 
+    # -- scenarios -------------------------------------------------------
+    def _ident(self, ident, what):
+        """ident: [m] (the same for every LP) or [count, m] -> the flat int64 array of the C ABI."""
+        a = np.asarray(ident, dtype=np.int64)
+        if a.ndim == 1:
+            a = np.tile(a, (self.count, 1))
+        if a.shape != (self.count, self.m):
+            raise LPGError(f"{what}: ident of shape {a.shape}, want [{self.m}] or [{self.count}, {self.m}]")
+        return np.ascontiguousarray(a).ravel()
+
+    def _rhs(self, rhs, lps, what):
+        """rhs: [len(lps), m], row c the right-hand side for LP lps[c] -> the packed float64 array of the C ABI."""
+        a = np.ascontiguousarray(rhs, dtype=np.float64)
+        if a.shape != (len(lps), self.m):
+            raise LPGError(f"{what}: rhs of shape {a.shape}, want [{len(lps)}, {self.m}]")
+        return a.ravel()
+
+    def scenario(self, src, rhs, ident):
+        """A new batch of len(src) children made on the device (include/lpg.h lpg_batch_scenario): child c is LP
+        src[c] as it stands, its column 0 restated for the right-hand side rhs[c]; ident[q][i] is the column of LP
+        q that was the unit vector e_i in the frame rhs is given in (the basis the LP was loaded with).
+        solve_dual() re-optimises the children. The engine returned is of this engine's class."""
+        src = np.ascontiguousarray(src, dtype=np.int64)
+        if src.ndim != 1:
+            raise LPGError(f"scenario: src of shape {src.shape}, want [n]")
+        idt, r = self._ident(ident, "scenario"), self._rhs(rhs, src, "scenario")
+        child = ctypes.c_void_p()
+        self._check(self.lib.lpg_batch_scenario(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
+                                                idt.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_double_p)),
+                    "lpg_batch_scenario")
+        return self._wrap_child(child, src, [0] * len(src))
+
+    def set_rhs(self, rhs, ident):
+        """Every LP's column 0 restated in place for its new right-hand side rhs[q] (include/lpg.h
+        lpg_batch_set_rhs); ident as scenario's, of this batch. The LPs start again as after load()."""
+        idt, r = self._ident(ident, "set_rhs"), self._rhs(rhs, range(self.count), "set_rhs")
+        self._check(self.lib.lpg_batch_set_rhs(self._b, idt.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_double_p)),
+                    "lpg_batch_set_rhs")
+
     def _shape_of(self, q):
         return self.m, self.ncols
 
@@ -545,7 +584,8 @@ class RaggedBatchEngine(BatchEngine):
     """BatchEngine.ragged(shapes): LPs of different shapes in one batch
     (include/lpg.h, "ragged batches"). LP q is an (m_q + nobj) x ncols_q tableau;
     load, set_objective and the artificial solves take one array per LP, get_rows
-    and get_basis return one per LP; solve, solve_dual, reserve_log, set_tolerances,
+    and get_basis return one per LP, scenario and set_rhs take one rhs per child or LP and
+    one ident per LP; solve, solve_dual, reserve_log, set_tolerances,
     get_log and info are BatchEngine's (info reports the largest m, ncols, ld and
     lds_bytes). The packing to and from the C ABI's flat arrays happens here."""
 
@@ -644,6 +684,21 @@ class RaggedBatchEngine(BatchEngine):
         keep, cp = self._packed_costs(costs, "set_objective")
         self._check(self.lib.lpg_batch_set_objective_packed(self._b, cp), "lpg_batch_set_objective_packed")
         del keep
+
+    def _ident(self, ident, what):
+        """ident[q]: [m_q], one array per LP."""
+        return self._flat(ident, f"{what} (ident)", lambda m, nc: (m,), np.int64)
+
+    def _rhs(self, rhs, lps, what):
+        """rhs[c]: [m of LP lps[c]], one array per entry of lps (an LP outside the batch is the library's to refuse)."""
+        rhs = list(rhs)
+        if len(rhs) != len(lps):
+            raise LPGError(f"{what}: {len(rhs)} right-hand sides for {len(lps)} LPs")
+        parts = [np.asarray(a, dtype=np.float64) for a in rhs]
+        for c, (a, q) in enumerate(zip(parts, lps)):
+            if a.ndim != 1 or (0 <= q < self.count and a.shape != (self.shapes[q][0],)):
+                raise LPGError(f"{what}: rhs[{c}] has shape {a.shape}, want ({self.shapes[q][0] if 0 <= q < self.count else 'm'},)")
+        return np.ascontiguousarray(np.concatenate(parts + [np.zeros(0)]))
 
     def get_rows(self) -> list:
         flat = np.zeros(sum((m + self.nobj) * nc for m, nc in self.shapes), dtype=np.float64)

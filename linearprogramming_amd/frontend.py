@@ -25,6 +25,10 @@ the reference binary's transcripts). Stages, each citing what it restates:
                    BatchEngine.branch + solve_dual ("Branching"),
                    optionally after rounds of Gomory cuts at the root
                    (BatchEngine.cut, DESIGN.md §3.7, "Cuts")
+* ``solve_scenarios``  models that differ only in their right-hand sides: the
+                   first solved, the others restated from its tableau on the
+                   device and re-optimised by the dual simplex
+                   (BatchEngine.scenario, DESIGN.md §3.7, "Scenarios")
 
 The variable table mirrors hashTable.c (PutVarItem replaces an existing key in
 place; GetVarItems walks buckets in hash order, VarHash hashTable.c:148-167).
@@ -807,6 +811,56 @@ def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase", r
     return out
 
 
+def solve_scenarios(sms, rule=None, device: int = 0) -> list:
+    """The optimum of every SMatrix of ``sms``, models that differ only in their right-hand sides (column 0 of
+    the standard-form rows; engine_arrays' rows beyond column 0, basis, cost, nc0 and nlack must be equal, or a
+    FrontendError names the first model that differs), warm-started on the device (include/lpg.h, "scenarios"):
+    ``sms[0]`` is solved as solve() solves it (the primal simplex, or two-phase where rows lack a basic column) in
+    a batch of one; scenario() makes one child per model, sms[0] included, from that solved tableau, the
+    right-hand sides stated in the frame of the basis the model was loaded with; one solve_dual() re-optimises
+    all of them. Every entry has ``method="scenario_dual"`` and the child's dual pivots as ``pivots``. Where the
+    base is not OPTIMAL, or its final basis still holds an artificial column (the dual simplex would not keep
+    that artificial at zero), or a column of the loaded basis has a cost (the restated objective would lack that
+    cost times the right-hand side), the result is solve_batch(sms, rule)'s instead."""
+    from . import _lib as L
+    from .engine import BatchEngine
+    if rule is None:
+        rule = L.RULE_DANTZIG
+    sms = list(sms)
+    if not sms:
+        return []
+    arrays = [engine_arrays(sm) for sm in sms]
+    rows, basis, cost, nc0, nlack = arrays[0]
+    for idx, (r, b, c, n0, nl) in enumerate(arrays[1:], 1):
+        if not (r.shape == rows.shape and (n0, nl) == (nc0, nlack) and np.array_equal(r[:, 1:], rows[:, 1:])
+                and np.array_equal(b, basis) and np.array_equal(c, cost)):
+            raise FrontendError(f"solve_scenarios: model {idx} differs from model 0 in more than its right-hand side")
+    m, nc = rows.shape
+    if cost[basis - 1].any():
+        return solve_batch(sms, rule)
+    T = np.zeros((1, m + 1, nc), dtype=np.float64)
+    T[0, :m] = rows
+    with BatchEngine(1, m, nc, device=device) as base:
+        base.load(T, basis[None])
+        if nlack:
+            res = base.solve_two_phase(nc0, cost, rule=rule)
+        else:
+            base.set_objective(cost)
+            res = base.solve(rule=rule)
+        if res[0].status != L.OPTIMAL or (base.get_basis()[0] >= nc0).any():
+            return solve_batch(sms, rule)
+        with base.scenario(np.zeros(len(sms), dtype=np.int64), np.array([a[0][:, 0] for a in arrays]), basis) as e:
+            res = e.solve_dual()
+            tabs, bas = e.get_rows(), e.get_basis()
+    out = []
+    for q, sm in enumerate(sms):
+        sol = LPSolution(res[q].status_name, int(res[q].pivots), method="scenario_dual")
+        if res[q].status == L.OPTIMAL:
+            _readout(sm, sol, res[q].objective, tabs[q, :m, 0], bas[q], nc)
+        out.append(sol)
+    return out
+
+
 def solve(sm: SMatrix, method: str = "two_phase", rule=None, device: int = 0) -> LPSolution:
     """The bridge's device solve (integration/lpg_bridge.c LPGSolveSMatrix) on liblpg:
     rows without a true unit basic column get artificials (two-phase by default,
@@ -998,7 +1052,8 @@ def solve_ilp_text(text: str, integer=None, *, int_tol: float = 1e-6, node_limit
 
 def main(argv=None) -> int:
     """``python -m linearprogramming_amd.frontend model.txt [--big-m] [--bland]``:
-    the reference's input file solved on the device, non-interactively."""
+    the reference's input file solved on the device, non-interactively
+    (many models that differ only in their right-hand sides: solve_scenarios)."""
     import argparse
     from . import _lib as L
     ap = argparse.ArgumentParser(description=main.__doc__)

@@ -78,7 +78,11 @@ extern "C" {
 
 /* ---- lpg_create flags ---- */
 #define LPG_FLAG_NO_LOG  0x1u  /* do not record the (entering, leaving) pivot log */
-#define LPG_FLAG_NO_SKIP 0x2u  /* update every column (no skipping of P[j] == 0 slices) */
+#define LPG_FLAG_NO_SKIP 0x2u  /* update every column (no skipping of P[j] == 0 slices). A context does so on its own
+                                  once lpg_load_rows has given it a -0 or a non-finite entry or lpg_solve_dual has run
+                                  (negative pivots make -0s): skipping a column is bit for bit the full update only
+                                  on a tableau free of both. lpg_generate, or loading the whole tableau clean, starts
+                                  again. Forced pivots on negative elements (lpg_pivot) are not tracked. */
 #define LPG_FLAG_BIG_M   0x4u  /* two objective rows: row m = M part, row m+1 = real part (Big-M) */
 #define LPG_FLAG_EAGER   0x8u  /* one rank-1 update pass per pivot instead of deferred (blocked) updates */
 

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/lpg.h"
@@ -70,6 +71,13 @@ struct lpg_ctx {
     bool pmr = false;             // k_pivot_block's geometry also holds for the multi-rank form (same on every rank)
     bool persist_x = false;       // multi-rank k_pivot_block over the owner-push exchange (attach_push)
     bool no_reorder = false;      // LPG_NO_REORDER=1: keep the caller's column order (no block-end column trade)
+    // Column skipping and the column trade are exact only on a tableau without
+    // -0 and without non-finite entries (exact_mode below): what was configured,
+    // and what the tableau has been seen to hold
+    int skip_cfg = 1;
+    bool no_reorder_cfg = false;
+    bool signed_zeros = false;    // a -0 or a non-finite entry was loaded, or the dual (negative pivots) has run
+    bool nonfinite = false;       // a non-finite entry was loaded
     int pb_nwg = 0, pb_cw = 0, pb_rw = 0;
     size_t pb_lds = 0;
     // region mode of the single-rank persistent launch (lpg_block.hip REG): the
@@ -487,9 +495,51 @@ static int clear_candidates(lpg_ctx *c) {
 
 static int region_setup(lpg_ctx *c);
 
+static void graph_drop(lpg_ctx *c);
+static int region_setup(lpg_ctx *c);
+
+// Skipping a column whose pivot-row entry is zero leaves t where the oracle
+// computes fma(-C_i, +-0, t): the same bits unless t is -0 (it becomes +0
+// unless the product is -0 too) or C_i is not finite (NaN). A tableau loaded
+// without -0 and without non-finite entries and pivoted on positive elements
+// only (the primal) never holds a -0, so there the skip is exact; the dual
+// pivots on negative elements (P_j = 0 / piv = -0). Once a context has seen
+// either, it updates every column, and region mode, whose slices rest on the
+// same premise, is left at the next region_setup. The column trade writes the
+// columns that entered the basis as unit vectors, which a non-finite C_i
+// turns into NaNs in the oracle: with a non-finite entry loaded the trade
+// stays off as well, on every rank of a partition alike (the ranks exchange
+// P in their common column order, so they decide together).
+// Called at a bootstrap, right after canonicalize(): the caller's column
+// order holds and nothing is pending.
+static int exact_mode(lpg_ctx *c) {
+    const int skip = (c->skip_cfg && !c->signed_zeros) ? 1 : 0;
+    if (skip != c->skip) {
+        c->skip = skip;
+        graph_drop(c);            // the captured launches hold the old flag
+    }
+    bool nf = c->nonfinite;
+    if (c->world > 1 && (c->nccl || c->have_hops)) {
+        const double mine = nf ? 1.0 : 0.0;
+        std::vector<double> all((size_t)c->world);
+        HIPCHK(c, hipMemcpyAsync(c->acc, &mine, sizeof mine, hipMemcpyHostToDevice, c->stream));
+        int rc = comm_allgather(c, c->acc, c->acc + 1, sizeof(double));
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(all.data(), c->acc + 1, all.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (double v : all) nf = nf || v != 0.0;
+    }
+    const bool nr = c->no_reorder_cfg || nf;
+    if (nr != c->no_reorder) {
+        c->no_reorder = nr;
+        graph_drop(c);
+    }
+    return 0;
+}
+
 static int bootstrap(lpg_ctx *c, int rule) {
     int rc = canonicalize(c);
-    if (rc || (rc = region_setup(c)) || (rc = clear_candidates(c))) return rc;
+    if (rc || (rc = exact_mode(c)) || (rc = region_setup(c)) || (rc = clear_candidates(c))) return rc;
     HIPCHK(c, hipMemsetAsync(c->st->slot, 0, sizeof(c->st->slot), c->stream));
     const Geo g = geo(c);
     if (launch_price(lau(c), g, rule, 0, c->st, 0, c->P, c->C[0], c->pp, c->pc, c->npp))
@@ -509,7 +559,7 @@ static int bootstrap(lpg_ctx *c, int rule) {
 // admits only row r (either sign, |T[r][k]| > eps_piv).
 static int bootstrap_forced(lpg_ctx *c, int rule, int64_t k, int64_t r) {
     int rc = canonicalize(c);
-    if (rc || (rc = region_setup(c)) || (rc = clear_candidates(c))) return rc;
+    if (rc || (rc = exact_mode(c)) || (rc = region_setup(c)) || (rc = clear_candidates(c))) return rc;
     HIPCHK(c, hipMemsetAsync(c->st->slot, 0, sizeof(c->st->slot), c->stream));
     if (launch_select(lau(c), geo(c), rule, true, c->st, 0, 0, c->P, c->C[1], c->C[0], c->pp, c->npp, c->basis,
                       c->part, c->nsel, k, r, c->pc, c->skip, defer_of(c, 0)))
@@ -548,7 +598,7 @@ static int cand_cap(const lpg_ctx *c) { return std::max(c->nsel, c->nsel_d); }
 static int region_setup(lpg_ctx *c) {
     if (!c->reg) return 0;
     if (c->world > 1 && !(c->persist_x && c->xmode)) return 0;   // the collectives' pair: region mode unused
-    if (c->world == 1 && c->units_known) return 0;
+    if (c->world == 1 && c->units_known && !c->signed_zeros) return 0;
     int ok = 1;
     if (!c->units_known) {
         HIPCHK(c, hipMemsetAsync(c->rok, 0xff, sizeof(int), c->stream));
@@ -557,6 +607,8 @@ static int region_setup(lpg_ctx *c) {
     } else {
         HIPCHK(c, hipMemsetAsync(c->rok, 0xff, sizeof(int), c->stream));   // known: nonzero
     }
+    // a tableau that may hold -0 or non-finite entries: no region mode (exact_mode)
+    if (c->signed_zeros) HIPCHK(c, hipMemsetAsync(c->rok, 0, sizeof(int), c->stream));
     if (c->world > 1) {
         int rc = comm_allgather(c, c->rok, c->rok + 1, sizeof(int));
         if (rc) return rc;
@@ -1037,7 +1089,7 @@ int lpg_create_dist(lpg_ctx **out, int device, int world, int rank, int64_t m, i
     const char *gr = getenv("LPG_GRAPH_RCCL");
     c->graph_comm = gr && atoi(gr);
     const char *ns = getenv("LPG_NO_SKIP");
-    c->skip = ((flags & LPG_FLAG_NO_SKIP) || (ns && atoi(ns))) ? 0 : 1;
+    c->skip = c->skip_cfg = ((flags & LPG_FLAG_NO_SKIP) || (ns && atoi(ns))) ? 0 : 1;
     const char *dk = getenv("LPG_DEFER");
     // default block: 64 pivots once this rank's tableau is >= 200 MB (the
     // flush dominates; k_flushw keeps 64-pivot flushes memory-bound), 32 below
@@ -1056,7 +1108,7 @@ int lpg_create_dist(lpg_ctx **out, int device, int world, int rank, int64_t m, i
     // live columns do (config 2: 105k -> 112k pivots/s without it, config 5:
     // 67k -> 69k, config 3: 25k -> 21k). LPG_NO_REORDER=0/1 decides instead.
     const char *nr = getenv("LPG_NO_REORDER");
-    c->no_reorder = nr ? atoi(nr) != 0 : (world == 1 && tbytes < 2e9);
+    c->no_reorder = c->no_reorder_cfg = nr ? atoi(nr) != 0 : (world == 1 && tbytes < 2e9);
     const char *sp = getenv("LPG_SLOW_PIVOT");
     c->fast_pivot = !(sp && atoi(sp));
     // the persistent pivot launch (LPG_PERSIST=0: the two-kernel pair) and its
@@ -1513,6 +1565,23 @@ int lpg_load_rows(lpg_ctx *c, int64_t row0, int64_t nrows, const double *rows, i
         return fail(c, LPG_ERR_ARG, "lpg_load_rows: bad arguments");
     int rc;
     if ((rc = use_device(c)) || (rc = canonicalize(c))) return rc;
+    // -0 or non-finite entries among the rows given (every row, not only this
+    // rank's: ranks given the same rows decide alike); a clean load of the
+    // whole tableau starts again (exact_mode)
+    {
+        bool sz = false, nf = false;
+        for (int64_t i = 0; i < nrows; i++) {
+            const double *row = rows + i * ld;
+            for (int64_t j = 0; j < c->ncols; j++) {
+                const double v = row[j];
+                nf |= !std::isfinite(v);
+                sz |= v == 0.0 && std::signbit(v);
+            }
+        }
+        const bool whole = row0 == 0 && nrows == c->m + c->nobj;
+        c->signed_zeros = (whole ? false : c->signed_zeros) || sz || nf;
+        c->nonfinite = (whole ? false : c->nonfinite) || nf;
+    }
     // canonicalize() queues work on c->stream (non-blocking): the synchronous
     // copies below go through the null stream and must not overtake it
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1624,6 +1693,7 @@ int lpg_generate(lpg_ctx *c, int64_t n, uint64_t seed, int kind) {
     if (launch_generate(lau(c), geo(c), n, seed, kind, c->basis)) return fail(c, LPG_ERR_DEVICE, "generate launch failed");
     c->poisoned = false;   // the whole tableau and the basis are rewritten
     c->units_known = true; // the generator writes exact unit columns for the slack / artificial basis
+    c->signed_zeros = c->nonfinite = false;   // and neither -0 nor non-finite entries (exact_mode)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return reset_state(c);
 }
@@ -1988,6 +2058,9 @@ int lpg_solve_dual(lpg_ctx *c, int64_t max_pivots, lpg_result *out) {
     for (int64_t j = 1; j <= c->nact; j++)
         if (obj[j] < -c->eps_opt)
             return fail(c, LPG_ERR_STATE, "lpg_solve_dual: basis not dual feasible (d_%lld = %g)", (long long)j, obj[j]);
+    // the dual pivots on negative elements: P_j = 0 / piv = -0 from here on (exact_mode)
+    c->signed_zeros = true;
+    if ((rc = exact_mode(c))) return rc;
     if (c->defer_k > 0 && c->nobj == 1) return solve_dual_deferred(c, max_pivots, out);
     const Geo g = geo(c);
     const Launch L = lau(c);

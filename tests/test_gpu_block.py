@@ -331,6 +331,8 @@ def _tied_lp(m, n, seed):
 @pytest.mark.parametrize("defer", [32, 64])
 @pytest.mark.parametrize("m,n,seed", [(300, 500, 3), (97, 1500, 4)])
 def test_pricing_key_ties(lpg, monkeypatch, wg, defer, m, n, seed):
+    """Dantzig, one objective row, an inexact quantised LP. The exact cases (every record form, the ratio
+    records, every pivot path, with a CPU census of where the ties fall) are tests/test_gpu_engine_ties.py's."""
     T, basis = _tied_lp(m, n, seed)
     assert _fits(m, n + m + 1, defer, wg)
     e = _engine(lpg, monkeypatch, m, n + m + 1, defer=defer, wg=wg)

@@ -12,7 +12,9 @@ a small integer, every operation exact, and most pivots tie. census() walks the
 oracle pivot by pivot and counts the ties by where the tied candidates sit in a
 256-thread argmin (different waves: index // 64 differ; the same thread:
 index % 256 equal), so the CPU tests can demand that the GPU cases are not
-vacuous.
+vacuous. A caller with another geometry passes its boundaries (census's
+`bounds`; tests/engine_tie_cases.py: the single-LP engine's row and column
+blocks, slices and ranks) and gets the ties that straddle them counted too.
 
 A case is a JSON-able dict; run_batch(spec) runs it on the device,
 run_oracle(spec) runs every LP through an Oracle of its own (computed once per
@@ -364,12 +366,28 @@ KEYS = ("pivots", "price", "price_xwave", "price_thread", "price_cls1", "price_t
         "ratio_zero", "ratio_xwave", "ratio_thread", "boundary")
 
 
-def _where(stats, what, idx):
-    """Count one tie of the candidates at positions idx of a 256-thread argmin."""
+def blocks_of(pos, b):
+    """The block each position falls in: b an int, blocks of that width (pos // b); b a sorted list of first
+    positions of the blocks after block 0 (the ranks of a row partition: [m * r // world for r in 1 .. world-1])."""
+    pos = np.asarray(pos)
+    return pos // b if isinstance(b, (int, np.integer)) else np.searchsorted(np.asarray(b), pos, side="right")
+
+
+def bounds_keys(bounds):
+    """The census keys that `bounds` adds: "<class>_x<name>" per boundary kind, class "ratio" or "price"."""
+    return [f"{what}_x{name}" for what, names in sorted((bounds or {}).items()) for name in names]
+
+
+def _where(stats, what, idx, bounds=None, pos=None):
+    """Count one tie of the candidates at positions idx of a 256-thread argmin. bounds: {name: b}, further boundary
+    kinds of this class (blocks_of): stats[what + "_x" + name] counts the ties whose candidates sit in more than one
+    block; pos: their positions in that geometry where they are not idx (a column's physical index j = idx + 1)."""
     idx = np.asarray(idx)
     stats[what] += 1
     stats[what + "_xwave"] += len(set((idx // 64).tolist())) > 1
     stats[what + "_thread"] += len(set((idx % 256).tolist())) < len(idx)
+    for name, b in (bounds or {}).items():
+        stats[f"{what}_x{name}"] += len(set(blocks_of(idx if pos is None else pos, b).tolist())) > 1
 
 
 def _argmin_ties(v, key):
@@ -439,7 +457,7 @@ def check_exact(R, m, scale):
         assert np.array_equal(2 * R, np.rint(2 * R)) and np.abs(A).max() <= 2.0 and np.abs(R).max() < 2 ** 20
 
 
-def _walk_primal(o, m, nobj, nact, rule, eps, scale, st, budget=20000):
+def _walk_primal(o, m, nobj, nact, rule, eps, scale, st, budget=20000, bounds=None):
     """lpo_solve on oracle o, one pivot per call, every choice redone in numpy and counted. Returns the status."""
     eps_piv, eps_opt = eps
     for _ in range(budget):
@@ -456,11 +474,11 @@ def _walk_primal(o, m, nobj, nact, rule, eps, scale, st, budget=20000):
         if r < 0:
             return UNBOUNDED
         if len(kt) > 1:
-            _where(st, "price", kt - 1)
+            _where(st, "price", kt - 1, (bounds or {}).get("price"), kt)
             st["price_cls1"] += cls == 1
         st["price_two_classes"] += len(present) > 1
         if len(rt) > 1:
-            _where(st, "ratio", rt)
+            _where(st, "ratio", rt, (bounds or {}).get("ratio"))
             st["ratio_pos" if theta > 0 else "ratio_zero"] += 1
         before = o.solve(0, rule).pivots
         res = o.solve(1, rule)
@@ -470,7 +488,7 @@ def _walk_primal(o, m, nobj, nact, rule, eps, scale, st, budget=20000):
     return ITER_LIMIT
 
 
-def _walk_dual(o, m, nact, eps, scale, st, budget=20000):
+def _walk_dual(o, m, nact, eps, scale, st, budget=20000, bounds=None):
     eps_piv, eps_opt = eps
     for _ in range(budget):
         R = o.get_rows()
@@ -483,9 +501,9 @@ def _walk_dual(o, m, nact, eps, scale, st, budget=20000):
         if k < 0:
             return INFEASIBLE
         if len(rt) > 1:
-            _where(st, "price", rt)                  # the leaving row plays pricing's part
+            _where(st, "price", rt, (bounds or {}).get("price"))   # the leaving row plays pricing's part
         if len(kt) > 1:
-            _where(st, "ratio", kt - 1)
+            _where(st, "ratio", kt - 1, (bounds or {}).get("ratio"), kt)
             st["ratio_pos" if R[m, k] > 0 else "ratio_zero"] += 1
         # solve_dual(1) would test dual feasibility again in front of every pivot, which one long call does not do
         # (tolerance setting (b) leaves it on the way): numpy's pivot is applied, and census() compares the log
@@ -494,16 +512,20 @@ def _walk_dual(o, m, nact, eps, scale, st, budget=20000):
     return ITER_LIMIT
 
 
-def census(T, basis, method, rule, eps=(1e-9, 1e-9), scale=1):
+def census(T, basis, method, rule, eps=(1e-9, 1e-9), scale=1, bounds=None):
     """One LP walked through the oracle a pivot at a time (solve(1) / solve_dual(1), get_rows in front of each),
     every pivot choice redone in numpy. Counts: pivots; price (pricing ties; the dual: leaving-row ties), of them
     price_xwave (tied candidates in different waves) and price_thread (in the same thread), price_cls1 (Big-M: ties
     among class-1 columns), price_two_classes (Big-M: pivots that priced both classes); ratio (ratio ties; the dual:
     entering-column ties) = ratio_pos (theta > 0) + ratio_zero, ratio_xwave, ratio_thread; boundary (pivots whose
     (k, r) differs under <= / >=). The index of a candidate is the column minus 1 (pricing, the dual's entering
-    column) or the row (ratio test, the dual's leaving row). The log must equal the whole method's on a fresh oracle."""
+    column) or the row (ratio test, the dual's leaving row). The log must equal the whole method's on a fresh oracle.
+    bounds: {"ratio": {name: b}, "price": {name: b}}, the boundaries of the caller's geometry per class (blocks_of;
+    rows are counted by row, columns by their physical index j, column 0 included, so for the dual "price" takes row
+    boundaries and "ratio" column boundaries): the keys bounds_keys(bounds) count the ties whose candidates fall on
+    both sides of one."""
     from oracle.lpo import Oracle
-    st = dict.fromkeys(KEYS, 0)
+    st = dict.fromkeys(list(KEYS) + bounds_keys(bounds), 0)
     nobj = 2 if method == "big_m" else 1
     m, nc = basis.shape[0], T.shape[1]
     N, n = nc - 1, nc - 1 - m
@@ -517,17 +539,17 @@ def census(T, basis, method, rule, eps=(1e-9, 1e-9), scale=1):
 
     o, ref = fresh(), fresh()
     if method == "primal":
-        status = _walk_primal(o, m, 1, N, rule, eps, scale, st)
+        status = _walk_primal(o, m, 1, N, rule, eps, scale, st, bounds=bounds)
         want = ref.solve(20000, rule)
     elif method == "dual":
-        status = _walk_dual(o, m, N, eps, scale, st)
+        status = _walk_dual(o, m, N, eps, scale, st, bounds=bounds)
         want = ref.solve_dual(20000)
     elif method == "two_phase":                      # lpo_solve_two_phase by hand
         cost = -T[m, 1:].copy()
         c1 = np.zeros(N)
         c1[af - 1:] = -1.0
         o.set_objective(c1)
-        status = _walk_primal(o, m, 1, N, rule, eps, scale, st)
+        status = _walk_primal(o, m, 1, N, rule, eps, scale, st, bounds=bounds)
         R = o.get_rows()
         if status == OPTIMAL and not R[m, 0] < -1e-9 * max(1.0, np.abs(R[:m, 0]).sum()):
             for i in range(m):
@@ -537,7 +559,7 @@ def census(T, basis, method, rule, eps=(1e-9, 1e-9), scale=1):
                         o.pivot(int(use[0]) + 1, i)
             o.set_active_columns(af - 1)
             o.set_objective(cost)
-            status = _walk_primal(o, m, 1, af - 1, rule, eps, scale, st)
+            status = _walk_primal(o, m, 1, af - 1, rule, eps, scale, st, bounds=bounds)
         else:
             status = INFEASIBLE
         want = ref.solve_two_phase(af, None, 20000, rule)
@@ -548,7 +570,7 @@ def census(T, basis, method, rule, eps=(1e-9, 1e-9), scale=1):
         cm[af - 1:] = -1.0
         o.set_objective_m(cm)
         o.set_objective(cr)
-        status = _walk_primal(o, m, 2, N, rule, eps, scale, st)
+        status = _walk_primal(o, m, 2, N, rule, eps, scale, st, bounds=bounds)
         R = o.get_rows()
         if status in (OPTIMAL, UNBOUNDED) and R[m, 0] < -1e-9 * max(1.0, np.abs(R[:m, 0]).sum()):
             status = INFEASIBLE
@@ -566,18 +588,21 @@ def census(T, basis, method, rule, eps=(1e-9, 1e-9), scale=1):
 _CENSUS = {}
 
 
-def census_of(s):
-    """census summed over the LPs of case s (computed once per spec), plus "maxlog", the longest log."""
-    key = json.dumps(s, sort_keys=True)
+def census_of(s, bounds=None):
+    """census summed over the LPs of case s (computed once per spec and bounds), plus "maxlog", the longest log,
+    and "minlog", the shortest."""
+    key = json.dumps([s, bounds], sort_keys=True)
     if key not in _CENSUS:
-        tot = dict.fromkeys(KEYS, 0)
-        tot["maxlog"] = 0
+        keys = list(KEYS) + bounds_keys(bounds)
+        tot = dict.fromkeys(keys, 0)
+        tot["maxlog"], tot["minlog"] = 0, 1 << 62
         for q in range(count_of(s)):
             T, basis = build_lp(s, q)
-            st = census(T, basis, s["method"], s["rule"], tuple(s["eps"]) if s["eps"] else (1e-9, 1e-9), s["scale"])
-            for k in KEYS:
+            st = census(T, basis, s["method"], s["rule"], tuple(s["eps"]) if s["eps"] else (1e-9, 1e-9), s["scale"], bounds)
+            for k in keys:
                 tot[k] += int(st[k])
             tot["maxlog"] = max(tot["maxlog"], st["loglen"])
+            tot["minlog"] = min(tot["minlog"], st["loglen"])
         _CENSUS[key] = tot
     return _CENSUS[key]
 

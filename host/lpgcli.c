@@ -26,18 +26,22 @@
  *          any HIP call; the parent only relays the host-staged collectives
  *          over socketpairs and never touches a GPU); rank r on device
  *          (D + r) mod #devices; rank 0 prints the JSON line
- *   lpgcli --synthetic M N --batch B [--dual | --kind ...] [--rule ...] [--pivots K] [--seed S]
+ *   lpgcli --synthetic M N --batch B [--dual | --kind ...] [--rule ...] [--pivots K] [--seed S] [--ranging]
  *          B LPs of that shape (seeds S, S + 1, ...) in one lpg_batch, one
  *          workgroup per LP; prints the counts per status, the total pivots
  *          and the LPs/s and pivots/s of the solve call; --kind artificial:
  *          lpg_batch_generate_artificial + lpg_batch_solve_two_phase (with
- *          --big-m: lpg_batch_create_big_m + lpg_batch_solve_big_m)
+ *          --big-m: lpg_batch_create_big_m + lpg_batch_solve_big_m);
+ *          --ranging: lpg_batch_ranging after the solve, ident the generator's
+ *          unit columns; adds "ranging" to the JSON line: the LPs ranged, the
+ *          finite ends per kind and an FNV-1a digest of the nine output arrays
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
  */
 #define _POSIX_C_SOURCE 200809L
 #include <errno.h>
+#include <math.h>
 #include <signal.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -67,7 +71,7 @@ static int usage(const char *argv0) {
     fprintf(stderr, "Usage:\n\t%s --synthetic M N [--seed S] [--kind dense|degenerate|artificial] [--rule dantzig|bland]"
                     " [--pivots K] [--device D] [--gpus P [--exchange push|host]]\n"
                     "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate|artificial [--big-m]] [--rule dantzig|bland] [--pivots K]"
-                    " [--seed S]\n"
+                    " [--seed S] [--ranging]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
                     "\t(--dual: the dual simplex; also with --synthetic (any --gpus) and --tableau;\n"
@@ -327,9 +331,60 @@ static int run_dist(const dist_args *a) {
     return rc;
 }
 
+/* FNV-1a, 64 bits, continued over `n` bytes */
+static uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
+    const unsigned char *c = (const unsigned char *)p;
+    for (size_t i = 0; i < n; i++) h = (h ^ c[i]) * 0x100000001b3ull;
+    return h;
+}
+
+/* --ranging: lpg_batch_ranging on the solved batch, ident the generator's unit columns; prints the "ranging"
+ * member of the JSON line: how many LPs were ranged, how many ends of each kind are finite, and the FNV-1a
+ * digest of the nine arrays' bytes in the order of lpg_ranging_t */
+static int print_ranging(lpg_batch *b, long long m, long long n, long long count, int two, const lpg_result *res) {
+    const size_t nb = (size_t)(count * m), nc = (size_t)(count * (n + m));
+    int64_t *ident = (int64_t *)malloc(nb * sizeof(int64_t));
+    double *d = (double *)malloc((3 * nb + 2 * nc) * sizeof(double));
+    int64_t *at = (int64_t *)malloc((2 * nb + 2 * nc) * sizeof(int64_t));
+    int rc = 1;
+    if (ident && d && at) {
+        for (long long q = 0; q < count; q++)
+            for (long long i = 0; i < m; i++)
+                ident[q * m + i] = !two ? 1 + n + i : (i & 1) ? 1 + n + (m + 1) / 2 + i / 2 : 1 + n + i / 2;
+        const lpg_ranging_t out = {d, d + nb, d + nb + nc, at, at + nc, d + nb + 2 * nc, d + 2 * nb + 2 * nc, at + 2 * nc,
+                                   at + 2 * nc + nb};
+        if (lpg_batch_ranging(b, ident, &out) != 0) {
+            fprintf(stderr, "ERROR: %s\n", lpg_batch_last_error(b));
+        } else {
+            long long ranged = 0, fin[4] = {0, 0, 0, 0};
+            for (long long q = 0; q < count; q++) ranged += res[q].status == LPG_OPTIMAL;
+            for (size_t j = 0; j < nc; j++) fin[0] += isfinite(out.cost_lo[j]), fin[1] += isfinite(out.cost_hi[j]);
+            for (size_t i = 0; i < nb; i++) fin[2] += isfinite(out.rhs_lo[i]), fin[3] += isfinite(out.rhs_hi[i]);
+            uint64_t h = 0xcbf29ce484222325ull;
+            h = fnv1a(h, out.dual, nb * 8);
+            h = fnv1a(h, out.cost_lo, nc * 8);
+            h = fnv1a(h, out.cost_hi, nc * 8);
+            h = fnv1a(h, out.cost_lo_at, nc * 8);
+            h = fnv1a(h, out.cost_hi_at, nc * 8);
+            h = fnv1a(h, out.rhs_lo, nb * 8);
+            h = fnv1a(h, out.rhs_hi, nb * 8);
+            h = fnv1a(h, out.rhs_lo_at, nb * 8);
+            h = fnv1a(h, out.rhs_hi_at, nb * 8);
+            printf(", \"ranging\": {\"ranged\": %lld, \"finite_cost_lo\": %lld, \"finite_cost_hi\": %lld, "
+                   "\"finite_rhs_lo\": %lld, \"finite_rhs_hi\": %lld, \"digest\": \"%016llx\"}",
+                   ranged, fin[0], fin[1], fin[2], fin[3], (unsigned long long)h);
+            rc = 0;
+        }
+    }
+    free(ident);
+    free(d);
+    free(at);
+    return rc;
+}
+
 /* --batch B: B synthetic LPs of one shape through lpg_batch */
 static int run_batch(long long m, long long n, long long count, unsigned long long seed, int kind, int dual, int bigm,
-                     int rule, long long pivots, int device) {
+                     int rule, long long pivots, int device, int ranging) {
     lpg_batch *b = NULL;
     lpg_result *res = (lpg_result *)malloc((size_t)(count > 0 ? count : 1) * sizeof(lpg_result));
     if (!res) return 1;
@@ -370,11 +425,13 @@ static int run_batch(long long m, long long n, long long count, unsigned long lo
            info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global", (long long)info.lds_bytes, info.chunk,
            bigm ? "big-m" : method_name(kind, dual), rule == LPG_RULE_BLAND && !dual ? "bland" : "dantzig");
     for (int s = 1; s <= 5; s++) printf("%s\"%s\": %lld", s > 1 ? ", " : "", status_name(s), by_status[s]);
-    printf("}, \"pivots\": %lld, \"seconds\": %.6f, \"lps_per_s\": %.3f, \"pivots_per_s\": %.3f}\n", total, dt,
+    printf("}, \"pivots\": %lld, \"seconds\": %.6f, \"lps_per_s\": %.3f, \"pivots_per_s\": %.3f", total, dt,
            dt > 0 ? (double)count / dt : 0.0, dt > 0 ? (double)total / dt : 0.0);
+    const int bad = ranging ? print_ranging(b, m, n, count, two, res) : 0;
+    printf("}\n");
     lpg_batch_destroy(b);
     free(res);
-    return 0;
+    return bad;
 }
 
 static char *read_all(const char *path) {
@@ -532,7 +589,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 20220518ull;
     int kind = LPG_GEN_DENSE, rule = LPG_RULE_DANTZIG, device = 0, gpus = 1, push = 1;
     const char *file = NULL, *lpfile = NULL;
-    int dump = 0, bigm = 0, dual = 0;
+    int dump = 0, bigm = 0, dual = 0, ranging = 0;
     for (int a = 1; a < argc; a++) {
         if (!strcmp(argv[a], "--synthetic") && a + 2 < argc) {
             m = atoll(argv[++a]);
@@ -546,6 +603,8 @@ int main(int argc, char **argv) {
             bigm = 1;
         } else if (!strcmp(argv[a], "--dual")) {
             dual = 1;
+        } else if (!strcmp(argv[a], "--ranging")) {
+            ranging = 1;
         } else if (!strcmp(argv[a], "--seed") && a + 1 < argc) {
             seed = strtoull(argv[++a], NULL, 10);
         } else if (!strcmp(argv[a], "--kind") && a + 1 < argc) {
@@ -572,8 +631,9 @@ int main(int argc, char **argv) {
     if (lpfile) return run_lp(lpfile, dump, dual ? LPF_DUAL : bigm ? LPF_BIG_M : LPF_TWO_PHASE, rule, device);
     if (batch >= 0) {
         if (!(m > 0 && n > 0) || file || gpus > 1) return usage(argv[0]);
-        return run_batch(m, n, batch, seed, kind, dual, bigm, rule, pivots, device);
+        return run_batch(m, n, batch, seed, kind, dual, bigm, rule, pivots, device, ranging);
     }
+    if (ranging) return usage(argv[0]);
     if (gpus > 1) {
         if (!(m > 0 && n > 0) || gpus > m || gpus > 64) return usage(argv[0]);
         const dist_args da = {m, n, pivots, seed, kind, rule, device, gpus, push, dual};

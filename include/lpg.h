@@ -681,6 +681,78 @@ int  lpg_batch_scenario(lpg_batch **child, lpg_batch *parent, int64_t n, const i
  * needs no new batch. Refusals as lpg_batch_scenario's. */
 int  lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs);
 
+/* ---- ranging: shadow prices, and how far costs and right-hand sides can move ----
+ *
+ * The sensitivity report of every solved LP of a batch, computed on the device
+ * (lpg_batch.hip k_batch_ranging, one workgroup per LP) from the tableau the
+ * solve left there: no tableau crosses the host. It works on batches of one
+ * shape and on ragged ones, refuses a Big-M batch (LPG_ERR_STATE) and changes
+ * nothing: statuses, pivots, logs, bases and tableaus stay as they were.
+ *
+ * Notation for LP q: T its tableau as lpg_batch_get_rows returns it, B its
+ * basis, 1..nact its active columns, N = ncols - 1, m its constraint rows,
+ * eps the batch's eps_piv, ident[i] in 1..N_q as in "scenarios" above (same
+ * meaning, same layout, same validation). "None" is 0 for a column index
+ * (columns are 1-based) and -1 for a row index.
+ *
+ * An LP whose status is not LPG_OPTIMAL is not ranged: every double of its
+ * outputs is NaN, every index none. For an LPG_OPTIMAL LP:
+ *
+ * Dual values. dual[i] = T[m][ident[i]], i = 0..m-1, the bits as they stand.
+ * This is the shadow price of row i where column ident[i] costs 0 (slacks, and
+ * artificials in phase II); otherwise the caller adds that column's cost.
+ *
+ * One ratio. Every bound is q = (-x) / a over candidates (x, a, index): the
+ * negation exact, the division the one IEEE division, nothing contracted. An
+ * entry is a candidate for the lower bound iff a > eps, for the upper bound
+ * iff a < -eps (both strict), and never one whose q is NaN. The lower bound is
+ * the largest candidate q, the upper bound the smallest; among candidates that
+ * compare equal (-0 and +0 do) the one with the smallest index wins, and its
+ * bits and its index are reported. With no candidate the bound is -inf or +inf
+ * and the index none. The order is total, so the result does not depend on how
+ * the candidates are grouped.
+ *
+ * Cost ranging. For column j = 1..N, at index j - 1 (the layout of the costs):
+ * the interval [cost_lo, cost_hi] of changes to the max-form cost c_j for
+ * which the basis stays optimal, and the column that limits each end.
+ *     j > nact:     (-inf, +inf), both indices none
+ *     j nonbasic (not in B, by membership, not by value):
+ *                   lo = -inf, index none; hi = T[m][j], hi_at = j
+ *     j basic in row r: the candidates are the columns k in 1..nact not in B,
+ *                   x = T[m][k], a = T[r][k], index k
+ * A row whose basic column lies behind nact (a kept artificial) ranges
+ * nothing. A basis that lists a column twice is the caller's error: the entry
+ * is that of one of the rows. The column that limits an end is the one that
+ * enters there.
+ *
+ * Right-hand-side ranging. For frame row i = 0..m-1, at index i (the layout of
+ * the bases): the interval [rhs_lo, rhs_hi] of changes to b_i for which the
+ * basis stays feasible. With h = ident[i] the candidates are the constraint
+ * rows r = 0..m-1, x = T[r][0], a = T[r][h], index r; the variable basic in
+ * the limiting row is the one that leaves there.
+ *
+ * Nothing is clamped: a d_k in [-eps_opt, 0) gives a bound on the wrong side
+ * of zero, as the numbers say. tests/ranging_cases.py restates all of this in
+ * numpy, operation for operation, and the device is held to it bit for bit. */
+typedef struct {
+    double  *dual;                                   /* m per LP, laid out as the bases */
+    double  *cost_lo, *cost_hi;                      /* ncols - 1 per LP, laid out as the costs */
+    int64_t *cost_lo_at, *cost_hi_at;
+    double  *rhs_lo, *rhs_hi;                        /* m per LP */
+    int64_t *rhs_lo_at, *rhs_hi_at;
+} lpg_ranging_t;
+/* The three groups (dual; the four cost_* arrays; the four rhs_* arrays) are
+ * each wanted or not as a whole: NULL pointers leave a group out, and it is
+ * then not computed. The layouts are count x m and count x (ncols - 1), dense,
+ * for a batch of one shape, and packed as lpg_batch_get_basis_packed's and
+ * lpg_batch_set_objective_packed's for a ragged one. Before any device work,
+ * with a message that names the call and the argument: `out` NULL, `ident`
+ * NULL, `b` NULL, a group given in part or no group at all (LPG_ERR_ARG, in
+ * this order, the first three without looking at the batch); then a Big-M
+ * batch (LPG_ERR_STATE); then an ident entry outside 1..N_q, naming the LP and
+ * the row (LPG_ERR_ARG). */
+int  lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *out);
+
 #ifdef __cplusplus
 }
 #endif

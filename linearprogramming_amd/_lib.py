@@ -76,6 +76,13 @@ class Branch(ctypes.Structure):
     _fields_ = [("row", ctypes.c_int64), ("col", ctypes.c_int64), ("value", ctypes.c_double)]
 
 
+class RangingOut(ctypes.Structure):
+    """lpg_ranging_t: nine output arrays, a group that is not wanted all NULL."""
+    _fields_ = [("dual", c_double_p), ("cost_lo", c_double_p), ("cost_hi", c_double_p),
+                ("cost_lo_at", c_int64_p), ("cost_hi_at", c_int64_p), ("rhs_lo", c_double_p), ("rhs_hi", c_double_p),
+                ("rhs_lo_at", c_int64_p), ("rhs_hi_at", c_int64_p)]
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, c_double_p, ctypes.c_size_t)
 
@@ -173,6 +180,7 @@ PROTOTYPES = [
     ("lpg_batch_scenario", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int64, c_int64_p,
                                           c_int64_p, c_double_p]),
     ("lpg_batch_set_rhs", ctypes.c_int, [ctypes.c_void_p, c_int64_p, c_double_p]),
+    ("lpg_batch_ranging", ctypes.c_int, [ctypes.c_void_p, c_int64_p, ctypes.POINTER(RangingOut)]),
 ]
 
 

@@ -60,6 +60,12 @@
 // right-hand sides. k_batch_scenario is grow_copy by no row plus
 // scenario_column, which restates column 0 from the columns that hold B^-1;
 // k_batch_set_rhs is scenario_column in place.
+//
+// Ranging (lpg_batch_ranging): the sensitivity report of the solved LPs.
+// k_batch_ranging reads the tableau the solve left in device memory and
+// reduces ratios under one total order (range_better): the cost ranges a wave
+// per basic row, the right-hand-side ranges a lane per frame row, the dual
+// values a gather. It writes only its own output arrays.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -1112,6 +1118,166 @@ __global__ __launch_bounds__(kBlock) void k_batch_set_rhs(BatchGeo g, const int6
     scenario_column(T, s.ld, s.m, sI, sR, T, s.ld, walk);
 }
 
+// ------------------------------------------------------------------------
+// ranging (include/lpg.h, "ranging"): dual values, and how far every cost and
+// every right-hand side of a solved LP can move before its basis changes.
+// Every bound is the largest (lower) or smallest (upper) q = (-x) / a over
+// candidates (x, a, index); a candidate for the lower bound iff a > eps_piv,
+// for the upper iff a < -eps_piv, never one whose q is NaN; equal q: the
+// smallest index. That order is total (indices are unique, NaNs are out), so
+// a lane's stride, the butterfly of a wave and any other grouping keep the
+// same winner, and tests/ranging_cases.py states it in numpy bit for bit.
+// ------------------------------------------------------------------------
+
+struct RangingOut {           // device arrays in the layouts of include/lpg.h; a group that is not wanted is null
+    double  *dual;
+    double  *cost_lo, *cost_hi;
+    int64_t *cost_lo_at, *cost_hi_at;
+    double  *rhs_lo, *rhs_hi;
+    int64_t *rhs_lo_at, *rhs_hi_at;
+};
+
+struct RangeRec {             // one running bound: its ratio and the candidate's index, -1 = no candidate yet
+    double  q;
+    int32_t at;
+};
+
+// candidate `a` takes the place of `b`; UP: the upper bound (smallest q), else the lower (largest q).
+// Branch-free, and the take is one select per field (lpg_device.h, the miscompile note).
+template <bool UP>
+__device__ __forceinline__ bool range_better(const RangeRec &a, const RangeRec &b) {
+    const bool ord = (UP ? a.q < b.q : a.q > b.q) | ((a.q == b.q) & (a.at < b.at));
+    return (a.at >= 0) & ((b.at < 0) | ord);
+}
+__device__ __forceinline__ void range_take(RangeRec &best, const RangeRec &c, bool t) {
+    best.q = t ? c.q : best.q;
+    best.at = t ? c.at : best.at;
+}
+
+// the candidate (x, a, at) offered to both running bounds
+__device__ __forceinline__ void range_offer(RangeRec &lo, RangeRec &hi, double x, double a, int32_t at, double eps) {
+    const double q = __ddiv_rn(-x, a);
+    const bool num = q == q;
+    const RangeRec cl{q, ((a > eps) & num) ? at : -1}, ch{q, ((a < -eps) & num) ? at : -1};
+    range_take(lo, cl, range_better<false>(cl, lo));
+    range_take(hi, ch, range_better<true>(ch, hi));
+}
+
+// the best record of the wave in every lane; the whole wave is active
+template <bool UP>
+__device__ __forceinline__ RangeRec range_wave(RangeRec c) {
+#pragma unroll
+    for (int mask = 32; mask > 0; mask >>= 1) {
+        RangeRec o;
+        o.q = __shfl_xor(c.q, mask, 64);
+        o.at = __shfl_xor(c.at, mask, 64);
+        range_take(c, o, range_better<UP>(o, c));
+    }
+    return c;
+}
+
+__device__ __forceinline__ double range_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// LP blockIdx.x of `g`. Dynamic LDS, the two phases one after the other in the same bytes:
+//   costs:             [objective row: ncols doubles][column -> the row it is basic in, or -1: ncols int32]
+//   right-hand sides:  [column 0: m doubles][ident: m int32]
+// Costs: wave w takes the basic rows w, w + 4, ..., its lanes stride the columns, one butterfly per bound and
+// row, no block barrier in the row loop; nonbasic and inert columns are filled lane = column. Right-hand sides:
+// a lane owns frame row i and walks the rows r of column ident[i] (neighbouring lanes read neighbouring
+// columns: slacks, artificials), so no cross-lane step.
+template <bool RG>
+__global__ __launch_bounds__(kBlock) void k_batch_ranging(BatchGeo g, const int64_t *ident, RangingOut o) {
+    extern __shared__ double smem[];
+    const LpGeo s = lp_geo<RG>(g, blockIdx.x, 1, 0);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t m = s.m, N = s.ncols - 1, nact = s.nact, ld = s.ld;
+    const double *T = g.T + s.t_off, *obj = T + m * ld;
+    const int64_t *basis = g.basis + s.b_off;
+    const double eps = g.eps_piv, inf = __longlong_as_double(0x7ff0000000000000ll);
+    ident += s.b_off;
+
+    if (g.lp[s.lp].status != OPTIMAL) {        // not ranged: NaN and "none" (column 0, row -1)
+        for (int64_t i = tid; i < m; i += kBlock) {
+            if (o.dual) o.dual[s.b_off + i] = range_nan();
+            if (o.rhs_lo) {
+                o.rhs_lo[s.b_off + i] = o.rhs_hi[s.b_off + i] = range_nan();
+                o.rhs_lo_at[s.b_off + i] = o.rhs_hi_at[s.b_off + i] = -1;
+            }
+        }
+        if (o.cost_lo)
+            for (int64_t j = tid; j < N; j += kBlock) {
+                o.cost_lo[s.c_off + j] = o.cost_hi[s.c_off + j] = range_nan();
+                o.cost_lo_at[s.c_off + j] = o.cost_hi_at[s.c_off + j] = 0;
+            }
+        return;
+    }
+
+    if (o.dual)
+        for (int64_t i = tid; i < m; i += kBlock) o.dual[s.b_off + i] = obj[ident[i]];
+
+    if (o.cost_lo) {
+        double *sObj = smem;
+        int32_t *sRow = (int32_t *)(smem + s.ncols);
+        for (int64_t j = tid; j <= N; j += kBlock) {
+            sObj[j] = obj[j];
+            sRow[j] = -1;
+        }
+        __syncthreads();
+        for (int64_t i = tid; i < m; i += kBlock) {
+            const int64_t bj = basis[i];
+            if (bj >= 1 && bj <= N) sRow[bj] = (int32_t)i;
+        }
+        __syncthreads();
+        double *lo = o.cost_lo + s.c_off, *hi = o.cost_hi + s.c_off;               // column j at [j - 1]
+        int64_t *lo_at = o.cost_lo_at + s.c_off, *hi_at = o.cost_hi_at + s.c_off;
+        for (int64_t j = 1 + tid; j <= N; j += kBlock) {
+            const bool inert = j > nact;
+            if (!inert && sRow[j] >= 0) continue;                 // basic: its row's wave stores it
+            lo[j - 1] = -inf;
+            lo_at[j - 1] = 0;
+            hi[j - 1] = inert ? inf : sObj[j];
+            hi_at[j - 1] = inert ? 0 : j;
+        }
+        for (int64_t r = wave; r < m; r += kBlock / 64) {         // wave-uniform
+            const int64_t j = basis[r];
+            if (j < 1 || j > nact || sRow[j] != (int32_t)r) continue;   // a kept artificial; a column listed twice: one row's
+            const double *row = T + r * ld;
+            RangeRec rl{0.0, -1}, rh{0.0, -1};
+            for (int64_t k = 1 + lane; k <= nact; k += 64)
+                if (sRow[k] < 0) range_offer(rl, rh, sObj[k], row[k], (int32_t)k, eps);
+            rl = range_wave<false>(rl);
+            rh = range_wave<true>(rh);
+            if (lane == 0) {
+                lo[j - 1] = rl.at < 0 ? -inf : rl.q;
+                lo_at[j - 1] = rl.at < 0 ? 0 : rl.at;
+                hi[j - 1] = rh.at < 0 ? inf : rh.q;
+                hi_at[j - 1] = rh.at < 0 ? 0 : rh.at;
+            }
+        }
+    }
+
+    if (o.rhs_lo) {
+        __syncthreads();                                          // the cost phase is done with the bytes
+        double *sB = smem;
+        int32_t *sI = (int32_t *)(smem + m);
+        for (int64_t i = tid; i < m; i += kBlock) {
+            sB[i] = T[i * ld];
+            sI[i] = (int32_t)ident[i];
+        }
+        __syncthreads();
+        for (int64_t i = tid; i < m; i += kBlock) {
+            const double *col = T + sI[i];
+            RangeRec rl{0.0, -1}, rh{0.0, -1};
+#pragma unroll 4
+            for (int64_t r = 0; r < m; r++) range_offer(rl, rh, sB[r], col[r * ld], (int32_t)r, eps);
+            o.rhs_lo[s.b_off + i] = rl.at < 0 ? -inf : rl.q;
+            o.rhs_lo_at[s.b_off + i] = rl.at;
+            o.rhs_hi[s.b_off + i] = rh.at < 0 ? inf : rh.q;
+            o.rhs_hi_at[s.b_off + i] = rh.at;
+        }
+    }
+}
+
 }  // namespace lpg
 
 // ---------------------------------------------------------------------------
@@ -1827,6 +1993,11 @@ int scenario_walk() { return env_is("LPG_SCENARIO_WALK", "tile") ? WALK_TILE : W
 size_t scenario_lds(int64_t m) { return (size_t)m * (sizeof(double) + sizeof(int32_t)); }
 constexpr int kScenarioMaxLds = LPG_BATCH_MAX_DIM * (int)(sizeof(double) + sizeof(int32_t));
 
+// dynamic LDS of a ranging workgroup: a double and an int32 per column in the cost phase, per row in the
+// right-hand-side phase, in the same bytes (k_batch_ranging); `dim` the larger of the batch's m and ncols
+size_t ranging_lds(int64_t dim) { return (size_t)dim * (sizeof(double) + sizeof(int32_t)); }
+constexpr int kRangingMaxLds = LPG_BATCH_MAX_DIM * (int)(sizeof(double) + sizeof(int32_t));
+
 // every ident entry of every LP of `b` names one of its columns 1..N
 int ident_ok(lpg_batch *b, const char *call, const int64_t *ident) {
     for (int64_t q = 0, at = 0; q < b->count; q++)
@@ -1915,6 +2086,66 @@ int lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs) {
     BHIPCHK(b, hipGetLastError());
     BHIPCHK(b, hipStreamSynchronize(b->stream));
     b->pivoted = false;
+    return 0;
+}
+
+int lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *out) {
+    const char *call = "lpg_batch_ranging";
+    // what does not depend on the batch first
+    if (!out) return bfail(b, LPG_ERR_ARG, "%s: out is NULL", call);
+    if (!ident) return bfail(b, LPG_ERR_ARG, "%s: ident is NULL", call);
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    const int ncost = !!out->cost_lo + !!out->cost_hi + !!out->cost_lo_at + !!out->cost_hi_at;
+    const int nrhs = !!out->rhs_lo + !!out->rhs_hi + !!out->rhs_lo_at + !!out->rhs_hi_at;
+    if (ncost % 4)
+        return bfail(b, LPG_ERR_ARG, "%s: out: %d of cost_lo, cost_hi, cost_lo_at, cost_hi_at given (all four or none)", call,
+                     ncost);
+    if (nrhs % 4)
+        return bfail(b, LPG_ERR_ARG, "%s: out: %d of rhs_lo, rhs_hi, rhs_lo_at, rhs_hi_at given (all four or none)", call, nrhs);
+    if (!out->dual && !ncost && !nrhs)
+        return bfail(b, LPG_ERR_ARG, "%s: out: none of dual, cost_*, rhs_* given (nothing to compute)", call);
+    if (b->nobj == 2) return wrong_kind(b, call);
+    if (int rc = ident_ok(b, call, ident)) return rc;
+    BHIPCHK(b, hipSetDevice(b->device));
+    if (int rc = b->ragged ? raise_lds<k_batch_ranging<true>>(b, "k_batch_ranging", kRangingMaxLds)
+                           : raise_lds<k_batch_ranging<false>>(b, "k_batch_ranging", kRangingMaxLds))
+        return rc;
+    // one allocation of 8-byte entries: ident, then the arrays of the wanted groups
+    const size_t nb = (size_t)b->b_total, nc = b->ragged ? (size_t)b->c_total : (size_t)b->count * (size_t)(b->ncols - 1);
+    const size_t total = nb + (out->dual ? nb : 0) + (ncost ? 4 * nc : 0) + (nrhs ? 4 * nb : 0);
+    DevBuf buf;
+    if (hipMalloc(&buf.p, total * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(ident and the outputs of %lld LPs) failed", call, (long long)b->count);
+    }
+    double *at = (double *)buf.p + nb;
+    auto take = [&at](bool want, size_t n) { double *p = want ? at : nullptr; if (want) at += n; return p; };
+    RangingOut o{};
+    o.dual = take(out->dual, nb);
+    o.cost_lo = take(ncost, nc);
+    o.cost_hi = take(ncost, nc);
+    o.cost_lo_at = (int64_t *)take(ncost, nc);
+    o.cost_hi_at = (int64_t *)take(ncost, nc);
+    o.rhs_lo = take(nrhs, nb);
+    o.rhs_hi = take(nrhs, nb);
+    o.rhs_lo_at = (int64_t *)take(nrhs, nb);
+    o.rhs_hi_at = (int64_t *)take(nrhs, nb);
+    BHIPCHK(b, hipMemcpyAsync(buf.p, ident, nb * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
+    const size_t lds = ranging_lds(std::max(b->m, b->ncols));
+    if (b->ragged)
+        hipLaunchKernelGGL(k_batch_ranging<true>, dim3((unsigned)b->count), dim3(kBlock), lds, b->stream, bgeo(b),
+                           (const int64_t *)buf.p, o);
+    else
+        hipLaunchKernelGGL(k_batch_ranging<false>, dim3((unsigned)b->count), dim3(kBlock), lds, b->stream, bgeo(b),
+                           (const int64_t *)buf.p, o);
+    BHIPCHK(b, hipGetLastError());
+    const struct { void *dst; const void *src; size_t n; } back[] = {
+        {out->dual, o.dual, nb},           {out->cost_lo, o.cost_lo, nc},       {out->cost_hi, o.cost_hi, nc},
+        {out->cost_lo_at, o.cost_lo_at, nc}, {out->cost_hi_at, o.cost_hi_at, nc}, {out->rhs_lo, o.rhs_lo, nb},
+        {out->rhs_hi, o.rhs_hi, nb},       {out->rhs_lo_at, o.rhs_lo_at, nb},   {out->rhs_hi_at, o.rhs_hi_at, nb}};
+    for (const auto &c : back)
+        if (c.dst) BHIPCHK(b, hipMemcpyAsync(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 

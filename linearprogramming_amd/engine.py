@@ -35,6 +35,26 @@ class SolveResult:
         return L.STATUS_NAMES.get(self.status, str(self.status))
 
 
+@dataclass
+class Ranging:
+    """What BatchEngine.ranging returns (include/lpg.h, "ranging"): per LP the dual values [m], the cost ranges
+    [ncols - 1] and the right-hand-side ranges [m], each range as its two ends and the index that limits each (a
+    column, 0 = none; a row, -1 = none). A batch of one shape gives 2-D arrays, a ragged one a list of arrays per
+    LP; a group that was not asked for is None. An LP that is not OPTIMAL has NaN and none everywhere."""
+    dual: object = None
+    cost_lo: object = None
+    cost_hi: object = None
+    cost_lo_at: object = None
+    cost_hi_at: object = None
+    rhs_lo: object = None
+    rhs_hi: object = None
+    rhs_lo_at: object = None
+    rhs_hi_at: object = None
+
+
+RANGING_FIELDS = ("dual", "cost_lo", "cost_hi", "cost_lo_at", "cost_hi_at", "rhs_lo", "rhs_hi", "rhs_lo_at", "rhs_hi_at")
+
+
 def _res(r: L.Result) -> SolveResult:
     return SolveResult(r.status, r.pivots, r.objective, r.entering, r.leaving, r.rule)
 
@@ -576,6 +596,31 @@ class BatchEngine:
         self._check(self.lib.lpg_batch_set_rhs(self._b, idt.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_double_p)),
                     "lpg_batch_set_rhs")
 
+    # -- ranging ---------------------------------------------------------
+    def _ranging_flat(self, ident, dual, cost, rhs) -> dict:
+        """lpg_batch_ranging into flat arrays: {field: array} for the fields of the wanted groups."""
+        idt = self._ident(ident, "ranging")
+        nb = sum(self._shape_of(q)[0] for q in range(self.count))
+        nc = sum(self._shape_of(q)[1] - 1 for q in range(self.count))
+        want = {"dual": dual, "cost": cost, "rhs": rhs}
+        out, flat = L.RangingOut(), {}
+        for f in RANGING_FIELDS:
+            if not want[f.split("_")[0]]:
+                continue
+            ints = f.endswith("_at")
+            flat[f] = np.zeros(nc if f.startswith("cost") else nb, dtype=np.int64 if ints else np.float64)
+            setattr(out, f, flat[f].ctypes.data_as(L.c_int64_p if ints else L.c_double_p))
+        self._check(self.lib.lpg_batch_ranging(self._b, idt.ctypes.data_as(L.c_int64_p), ctypes.byref(out)),
+                    "lpg_batch_ranging")
+        return flat
+
+    def ranging(self, ident, *, dual: bool = True, cost: bool = True, rhs: bool = True) -> Ranging:
+        """Shadow prices and cost / right-hand-side ranges of every LP, computed on the device from the solved
+        tableaus (include/lpg.h lpg_batch_ranging); ident as scenario's. Each of the three groups can be left
+        out (then its fields are None and it is not computed). The batch is not changed."""
+        flat = self._ranging_flat(ident, dual, cost, rhs)
+        return Ranging(**{f: a.reshape(self.count, -1) for f, a in flat.items()})
+
     def _shape_of(self, q):
         return self.m, self.ncols
 
@@ -585,7 +630,7 @@ class RaggedBatchEngine(BatchEngine):
     (include/lpg.h, "ragged batches"). LP q is an (m_q + nobj) x ncols_q tableau;
     load, set_objective and the artificial solves take one array per LP, get_rows
     and get_basis return one per LP, scenario and set_rhs take one rhs per child or LP and
-    one ident per LP; solve, solve_dual, reserve_log, set_tolerances,
+    one ident per LP, ranging takes one ident per LP and returns one array per LP in every field; solve, solve_dual, reserve_log, set_tolerances,
     get_log and info are BatchEngine's (info reports the largest m, ncols, ld and
     lds_bytes). The packing to and from the C ABI's flat arrays happens here."""
 
@@ -699,6 +744,12 @@ class RaggedBatchEngine(BatchEngine):
             if a.ndim != 1 or (0 <= q < self.count and a.shape != (self.shapes[q][0],)):
                 raise LPGError(f"{what}: rhs[{c}] has shape {a.shape}, want ({self.shapes[q][0] if 0 <= q < self.count else 'm'},)")
         return np.ascontiguousarray(np.concatenate(parts + [np.zeros(0)]))
+
+    def ranging(self, ident, *, dual: bool = True, cost: bool = True, rhs: bool = True) -> Ranging:
+        """BatchEngine.ranging with one ident array per LP; every field is a list of one array per LP."""
+        flat = self._ranging_flat(ident, dual, cost, rhs)
+        return Ranging(**{f: self._split(a, (lambda m, nc: (nc - 1,)) if f.startswith("cost") else (lambda m, nc: (m,)))
+                          for f, a in flat.items()})
 
     def get_rows(self) -> list:
         flat = np.zeros(sum((m + self.nobj) * nc for m, nc in self.shapes), dtype=np.float64)

@@ -811,6 +811,83 @@ def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase", r
     return out
 
 
+@dataclass
+class LPSensitivity(LPSolution):
+    """sensitivity_batch's result: the LPSolution and, for an OPTIMAL model, its sensitivity report."""
+    basis: list = field(default_factory=list)        # the column basic in each standard-form row, by name
+    shadow: list = field(default_factory=list)       # dz/db_i per standard-form row, in the user's objective sense
+    rhs_range: list = field(default_factory=list)    # per row: (lowest b_i, highest b_i, (who leaves at each end))
+    cost_range: dict = field(default_factory=dict)   # column -> (lowest c_j, highest c_j, (who enters at each end))
+
+
+def _column_name(sm: SMatrix, j: int, nc0: int):
+    """The name of engine column j (1-based): a standard-form column, or an artificial added for a lacking row."""
+    return sm.display_names[j - 1] if j < nc0 else f"artificial{j - nc0 + 1}"
+
+
+def sensitivity_batch(sms, rule=None, device: int = 0) -> list:
+    """solve_batch(sms, rule) and the sensitivity report of every model, computed on the device from the solved
+    tableaus (include/lpg.h, "ranging"): the same grouping by shape and the same methods (the plain primal
+    simplex, or two-phase where rows lack a basic column), one ranging() call per group. Every entry is an
+    LPSensitivity whose LPSolution fields equal solve_batch's bit for bit. For an OPTIMAL model, with ident =
+    engine_arrays' basis (the unit column of every standard-form row):
+
+    * ``basis[i]``: the column basic in row i at the optimum, by display name;
+    * ``shadow[i]`` = (dual[i] + cost of column ident[i]) / zcoef: the change of ``z`` per unit of the
+      standard-form right-hand side b_i, in the user's objective sense (a min model's sign restored, as ``z``);
+    * ``rhs_range[i]`` = (b_i + lo, b_i + hi, (a, b)): the values of b_i between which the optimal basis stays
+      feasible; a / b name the column basic in the row that limits the low / high end (the variable that leaves
+      there), None where that end is infinite;
+    * ``cost_range[name]`` = (c_j + lo, c_j + hi, (a, b)) for the standard-form columns: the values of the cost
+      c_j between which the basis stays optimal, and the column that enters at each end or None. The costs are
+      in MAX FORM, the ones SMatrix.costs holds: for a min model they are the negated user costs, and for a
+      primed (x <= 0) column the cost of the substituted variable.
+
+    The other models get the LPSolution fields alone."""
+    from . import _lib as L
+    from .engine import BatchEngine
+    if rule is None:
+        rule = L.RULE_DANTZIG
+    sms = list(sms)
+    arrays = [engine_arrays(sm) for sm in sms]
+    out = [None] * len(sms)
+    for (m, nc0, nlack), members in _groups(arrays).items():
+        nc = nc0 + nlack
+        T = np.zeros((len(members), m + 1, nc), dtype=np.float64)
+        for q, idx in enumerate(members):
+            T[q, :m] = arrays[idx][0]
+        ident = np.array([arrays[idx][1] for idx in members], dtype=np.int64)
+        cost = np.array([arrays[idx][2] for idx in members], dtype=np.float64)
+        with BatchEngine(len(members), m, nc, device=device) as e:
+            e.load(T, ident)
+            if nlack == 0:
+                e.set_objective(cost)
+                res, used = e.solve(rule=rule), "primal"
+            else:
+                res, used = e.solve_two_phase(nc0, cost, rule=rule), "two_phase"
+            rows, bas = e.get_rows(), e.get_basis()
+            rg = e.ranging(ident)
+        for q, idx in enumerate(members):
+            r, sm = res[q], sms[idx]
+            sol = LPSensitivity(r.status_name, int(r.pivots), method=used)
+            out[idx] = sol
+            if r.status != L.OPTIMAL:
+                continue
+            _readout(sm, sol, r.objective, rows[q, :m, 0], bas[q], nc)
+            name = lambda j: _column_name(sm, int(j), nc0)
+            zc, b, c = _dec(sm.zcoef), arrays[idx][0][:, 0], cost[q]
+            sol.basis = [name(j) for j in bas[q]]
+            sol.shadow = [float((rg.dual[q, i] + c[ident[q, i] - 1]) / zc) for i in range(m)]
+            leaves = lambda r_: None if r_ < 0 else name(bas[q, r_])
+            sol.rhs_range = [(float(b[i] + rg.rhs_lo[q, i]), float(b[i] + rg.rhs_hi[q, i]),
+                              (leaves(rg.rhs_lo_at[q, i]), leaves(rg.rhs_hi_at[q, i]))) for i in range(m)]
+            enters = lambda k: None if k < 1 else name(k)
+            sol.cost_range = {name(j): (float(c[j - 1] + rg.cost_lo[q, j - 1]), float(c[j - 1] + rg.cost_hi[q, j - 1]),
+                                        (enters(rg.cost_lo_at[q, j - 1]), enters(rg.cost_hi_at[q, j - 1])))
+                              for j in range(1, nc0)}
+    return out
+
+
 def solve_scenarios(sms, rule=None, device: int = 0) -> list:
     """The optimum of every SMatrix of ``sms``, models that differ only in their right-hand sides (column 0 of
     the standard-form rows; engine_arrays' rows beyond column 0, basis, cost, nc0 and nlack must be equal, or a

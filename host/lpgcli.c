@@ -35,6 +35,12 @@
  *          --ranging: lpg_batch_ranging after the solve, ident the generator's
  *          unit columns; adds "ranging" to the JSON line: the LPs ranged, the
  *          finite ends per kind and an FNV-1a digest of the nine output arrays
+ *   lpgcli --assign NR NC --batch B [--max] [--seed S] [--range R] [--device D]
+ *          B assignment problems of NR x NC (lpg_assign_generate: integer costs
+ *          in 0..R-1, default 100, seeds S, S + 1, ...) by the Hungarian method
+ *          in one launch; prints the shape, tier, form, the counts per status,
+ *          the total steps, an FNV-1a digest of col / u / v and the time of the
+ *          solve call
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
@@ -72,11 +78,12 @@ static int usage(const char *argv0) {
                     " [--pivots K] [--device D] [--gpus P [--exchange push|host]]\n"
                     "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate|artificial [--big-m]] [--rule dantzig|bland] [--pivots K]"
                     " [--seed S] [--ranging]\n"
+                    "\t%s --assign NR NC --batch B [--max] [--seed S] [--range R]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
                     "\t(--dual: the dual simplex; also with --synthetic (any --gpus) and --tableau;\n"
                     "\t --kind artificial: the two-phase method)\n",
-            argv0, argv0, argv0, argv0, argv0);
+            argv0, argv0, argv0, argv0, argv0, argv0);
     return 2;
 }
 
@@ -434,6 +441,59 @@ static int run_batch(long long m, long long n, long long count, unsigned long lo
     return bad;
 }
 
+/* --assign NR NC --batch B: B generated assignment problems through lpg_assign */
+static int run_assign(long long nr, long long nc, long long count, unsigned long long seed, long long range, int maximize,
+                      int device) {
+    lpg_assign *a = NULL;
+    if (lpg_assign_create(&a, device, count, nr, nc, maximize ? LPG_ASSIGN_MAXIMIZE : 0) != 0 ||
+        lpg_assign_generate(a, seed, range) != 0) {
+        fprintf(stderr, "ERROR: %s\n", lpg_assign_last_error(a));
+        lpg_assign_destroy(a);
+        return 1;
+    }
+    lpg_assign_result *res = (lpg_assign_result *)malloc((size_t)count * sizeof(lpg_assign_result));
+    int64_t *col = (int64_t *)malloc((size_t)(count * nr) * sizeof(int64_t));
+    double *u = (double *)malloc((size_t)(count * nr) * sizeof(double));
+    double *v = (double *)malloc((size_t)(count * nc) * sizeof(double));
+    int rc = 1;
+    if (res && col && u && v) {
+        const double t0 = now();
+        rc = lpg_assign_solve(a, res);
+        const double dt = now() - t0;
+        if (rc == 0) rc = lpg_assign_get(a, 0, count, col, u, v);
+        if (rc != 0) {
+            fprintf(stderr, "ERROR: %s\n", lpg_assign_last_error(a));
+            rc = 1;
+        } else {
+            long long by_status[6] = {0, 0, 0, 0, 0, 0}, steps = 0;
+            for (long long q = 0; q < count; q++) {
+                if (res[q].status >= 0 && res[q].status <= 5) by_status[res[q].status]++;
+                steps += (long long)res[q].steps;
+            }
+            uint64_t h = 0xcbf29ce484222325ull;
+            h = fnv1a(h, col, (size_t)(count * nr) * 8);
+            h = fnv1a(h, u, (size_t)(count * nr) * 8);
+            h = fnv1a(h, v, (size_t)(count * nc) * 8);
+            lpg_assign_info_t info;
+            lpg_assign_info(a, &info);
+            printf("{\"nr\": %lld, \"nc\": %lld, \"batch\": %lld, \"sense\": \"%s\", \"tier\": \"%s\", \"form\": \"%s\", "
+                   "\"lds_bytes\": %lld, \"statuses\": {\"OPTIMAL\": %lld, \"INFEASIBLE\": %lld}, \"steps\": %lld, "
+                   "\"digest\": \"%016llx\", \"seconds\": %.6f, \"problems_per_s\": %.3f}\n",
+                   (long long)info.nr, (long long)info.nc, (long long)info.count, maximize ? "max" : "min",
+                   info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global",
+                   info.form == LPG_ASSIGN_FORM_WAVE ? "wave" : "workgroup", (long long)info.lds_bytes,
+                   by_status[LPG_OPTIMAL], by_status[LPG_INFEASIBLE], steps, (unsigned long long)h, dt,
+                   dt > 0 ? (double)count / dt : 0.0);
+        }
+    }
+    free(res);
+    free(col);
+    free(u);
+    free(v);
+    lpg_assign_destroy(a);
+    return rc;
+}
+
 static char *read_all(const char *path) {
     FILE *f = fopen(path, "rb");
     if (!f) {
@@ -585,15 +645,23 @@ static int load_tableau_file(lpg_ctx **ctx, const char *path, int device) {
 }
 
 int main(int argc, char **argv) {
-    long long m = 0, n = 0, pivots = (long long)1 << 40, batch = -1;
+    long long m = 0, n = 0, pivots = (long long)1 << 40, batch = -1, anr = 0, anc = 0, range = 100;
     unsigned long long seed = 20220518ull;
     int kind = LPG_GEN_DENSE, rule = LPG_RULE_DANTZIG, device = 0, gpus = 1, push = 1;
     const char *file = NULL, *lpfile = NULL;
-    int dump = 0, bigm = 0, dual = 0, ranging = 0;
+    int dump = 0, bigm = 0, dual = 0, ranging = 0, assign = 0, maximize = 0;
     for (int a = 1; a < argc; a++) {
         if (!strcmp(argv[a], "--synthetic") && a + 2 < argc) {
             m = atoll(argv[++a]);
             n = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--assign") && a + 2 < argc) {
+            assign = 1;
+            anr = atoll(argv[++a]);
+            anc = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--max")) {
+            maximize = 1;
+        } else if (!strcmp(argv[a], "--range") && a + 1 < argc) {
+            range = atoll(argv[++a]);
         } else if (!strcmp(argv[a], "--tableau") && a + 1 < argc) {
             file = argv[++a];
         } else if ((!strcmp(argv[a], "--lp") || !strcmp(argv[a], "--lp-dump")) && a + 1 < argc) {
@@ -628,6 +696,11 @@ int main(int argc, char **argv) {
         }
     }
     if (dual && (bigm || kind == LPG_GEN_ARTIFICIAL)) return usage(argv[0]);
+    if (assign) {
+        if (batch < 1 || m || n || file || lpfile || gpus > 1 || dual || bigm || ranging) return usage(argv[0]);
+        return run_assign(anr, anc, batch, seed, range, maximize, device);
+    }
+    if (maximize) return usage(argv[0]);
     if (lpfile) return run_lp(lpfile, dump, dual ? LPF_DUAL : bigm ? LPF_BIG_M : LPF_TWO_PHASE, rule, device);
     if (batch >= 0) {
         if (!(m > 0 && n > 0) || file || gpus > 1) return usage(argv[0]);

@@ -753,6 +753,128 @@ typedef struct {
  * the row (LPG_ERR_ARG). */
 int  lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *out);
 
+/* ---- assignment: batches of n x n (and nr x nc) assignment problems ----
+ *
+ * The reference's README lists the assignment problem by the Hungarian method
+ * among the things it meant to solve. Stated as an LP it has nr + nc equality
+ * rows and nr * nc columns, an O(n^3) tableau for an O(n^2) problem at a vertex
+ * as degenerate as they come. An lpg_assign holds `count` cost matrices of one
+ * shape instead, nr rows by nc columns with 1 <= nr <= nc <= LPG_BATCH_MAX_DIM,
+ * row-major fp64, and solves them in one launch by the primal-dual (shortest
+ * augmenting path) Hungarian method (lpg_assign.hip): every row is assigned to
+ * a distinct column and the sum of the chosen costs is minimal, or maximal with
+ * LPG_ASSIGN_MAXIMIZE. Only subtraction, addition and comparison are used, so a
+ * host restatement reproduces every bit (tests/assign_cases.py). Ragged
+ * assignment batches are not provided.
+ *
+ * Costs. An entry of +inf forbids the pair. A maximisation negates the finite
+ * costs as they are loaded, which is exact (+inf still forbids), and negates u
+ * and v back on the way out. NaN, -inf and finite entries above
+ * LPG_ASSIGN_COST_CAP = 2^1000 in magnitude are refused by lpg_assign_load
+ * (LPG_ERR_ARG, the message names the problem and the entry) before any device
+ * work. The cap keeps every potential finite: in exact arithmetic -v[j] is the
+ * length of an alternating path of at most 2 nr <= 2^14 edges, each a cost of
+ * magnitude <= cap, so |v[j]| <= 2^14 cap and |u[i]| <= cap + max |v| < 2^1015;
+ * a problem makes fewer than 2^41 roundings, each off by at most 2^-53 of a
+ * magnitude below 2^1016, which moves those bounds by less than a factor of
+ * two, and 2^1017 is far below the overflow threshold 2^1024. With finite u
+ * and v no reduced cost is NaN (+inf minus a finite number is +inf) and delta
+ * is always finite.
+ *
+ * The algorithm, operation for operation. C is the matrix as loaded (negated
+ * for a maximisation). "None" is -1. u[nr] and v[nc] start at 0.0, rowof[nc]
+ * at none, steps at 0. For row i = 0 .. nr-1:
+ *   1. minv[j] = +inf, way[j] = none, used[j] = false for every j; i0 = i,
+ *      j0 = none.
+ *   2. Step (steps = steps + 1):
+ *        if j0 is a column, used[j0] = true;
+ *        for every unused j: cur = (C[i0][j] - u[i0]) - v[j], two roundings in
+ *          this order; if cur < minv[j] (strict): minv[j] = cur, way[j] = j0;
+ *        j1 = the unused column with the smallest minv under `<` (-0 and +0
+ *          compare equal), ties to the smallest j; delta = minv[j1], the bits
+ *          as they stand;
+ *        no unused column with minv < +inf: the problem is LPG_INFEASIBLE and
+ *          ends here, u and v as they stand.
+ *   3. Update, one rounding each:
+ *        u[i] = u[i] + delta;
+ *        for every used j: u[rowof[j]] = u[rowof[j]] + delta, v[j] = v[j] - delta;
+ *        for every unused j: minv[j] = minv[j] - delta;
+ *        j0 = j1; if rowof[j0] is a row: i0 = rowof[j0], go to 2.
+ *   4. Augment: while j0 is a column: rowof[j0] = (way[j0] is a column ?
+ *      rowof[way[j0]] : i), then j0 = way[j0].
+ * Row i's search marks a new column used in every step and ends at the first
+ * free one, so it makes at most i + 1 steps and steps <= nr (nr + 1) / 2,
+ * whatever the arithmetic does: a launch is bounded without relaunches.
+ *
+ * Per problem: status (LPG_OPTIMAL or LPG_INFEASIBLE); col[nr], the 0-based
+ * column of every row, -1 throughout for an infeasible problem; u[nr] and
+ * v[nc] in the caller's sense (for a maximisation the negation of each, so 0.0
+ * comes back as -0.0); objective = 0.0, then for i ascending objective +
+ * (the caller's C[i][col[i]]), one rounding per addition, NaN if infeasible;
+ * steps. On integer costs the certificate holds exactly: u[i] + v[j] <=
+ * C[i][j] with equality on assigned pairs, v <= 0, and v[j] == 0 on unassigned
+ * columns (a minimisation; mirrored for a maximisation).
+ *
+ * Two points decide the bits. The reduced costs are non-negative in exact
+ * arithmetic only: in fp64 a minv can be slightly negative or -0, so the
+ * argmin does not use block_argmin_cand's packed key ("the bits of theta >=
+ * 0"); it maps the bits to a total order with -0 and +0 made equal FOR THE KEY
+ * ONLY, and delta is the winner's own bits, because -0 + -0 and -0 + +0 differ.
+ * And every compare-and-keep is a branch-free per-field select (lpg_device.h
+ * tells why).
+ *
+ * Forms. nc <= 64: one wave per problem, four problems per workgroup, a column
+ * per lane, column state in registers, C and u in LDS (the wave form). Else one
+ * workgroup per problem, columns strided over 256 threads, their state in
+ * registers up to 256 columns and in LDS beyond (in device memory where even
+ * that does not fit); C in LDS where u, C and that state fit the 150 KiB
+ * dynamic LDS cap (LPG_BATCH_TIER_LDS, up to 138 x 138), else in device memory
+ * with one coalesced row read per step (LPG_BATCH_TIER_GLOBAL). Env
+ * LPG_ASSIGN_TIER=global forces the second tier (and with it the workgroup
+ * form, the only one that has it), env LPG_ASSIGN_FORM=workgroup the workgroup
+ * form at nc <= 64; both are read by lpg_assign_create. Every form computes the same bits.
+ *
+ * Every argument is checked on the host before any device work: the device is
+ * first touched by the first lpg_assign_load, _generate or _solve that passes
+ * its checks. The messages name the call and the first offending index; NULL
+ * handles are errors (lpg_assign_last_error(NULL): this thread's last one).
+ * One batch per host thread; not reentrant. */
+#define LPG_ASSIGN_MAXIMIZE        0x1u
+#define LPG_ASSIGN_FORM_WAVE       0
+#define LPG_ASSIGN_FORM_WORKGROUP  1
+#define LPG_ASSIGN_COST_CAP        0x1p1000
+
+typedef struct lpg_assign lpg_assign;
+typedef struct { int32_t status, pad; int64_t steps; double objective; } lpg_assign_result;
+typedef struct {
+    int64_t count, nr, nc;
+    int32_t tier;                 /* LPG_BATCH_TIER_*: where C lives while a problem runs */
+    int32_t form;                 /* LPG_ASSIGN_FORM_* */
+    int64_t lds_bytes;            /* dynamic LDS of one workgroup */
+    double  kernel_ms;            /* device time of the last lpg_assign_solve's kernel (events around the launch) */
+} lpg_assign_info_t;
+
+/* count >= 1 problems of nr x nc, 1 <= nr <= nc <= LPG_BATCH_MAX_DIM; flags: 0
+ * or LPG_ASSIGN_MAXIMIZE. Anything else: LPG_ERR_ARG and *out = NULL. */
+int  lpg_assign_create(lpg_assign **out, int device, int64_t count, int64_t nr, int64_t nc, uint32_t flags);
+/* Problems [first, first + n), n >= 1: n x nr rows of nc costs at pitch ld >=
+ * nc. Refused as a whole (nothing is loaded) on a bad entry, see "Costs". */
+int  lpg_assign_load(lpg_assign *a, int64_t first, int64_t n, const double *costs, int64_t ld);
+/* Problem q, entry (i, j) = floor(uniform01(seed + q, i * nc + j) * range),
+ * the engine's generator draw (oracle lpo_uniform): exact integers in
+ * 0..range-1; range in 1..2^53. */
+int  lpg_assign_generate(lpg_assign *a, uint64_t seed, int64_t range);
+/* Solves every problem, whatever an earlier call found; out[count] may be
+ * NULL. LPG_ERR_STATE while a problem has no costs. May be called again after
+ * another load. */
+int  lpg_assign_solve(lpg_assign *a, lpg_assign_result *out);
+/* Of problems [first, first + n) after a solve: col n x nr, u n x nr, v n x nc,
+ * dense; each may be NULL, not all three. */
+int  lpg_assign_get(lpg_assign *a, int64_t first, int64_t n, int64_t *col, double *u, double *v);
+int  lpg_assign_info(const lpg_assign *a, lpg_assign_info_t *out);
+const char *lpg_assign_last_error(const lpg_assign *a);
+void lpg_assign_destroy(lpg_assign *a);                        /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

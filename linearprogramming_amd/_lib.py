@@ -29,6 +29,9 @@ BATCH_TIER_LDS, BATCH_TIER_GLOBAL = 0, 1
 BATCH_MAX_DIM = 8192
 BRANCH_MOST_FRACTIONAL, BRANCH_FIRST = 0, 1
 BATCH_MAX_CUTS = 1024
+ASSIGN_MAXIMIZE = 0x1
+ASSIGN_FORM_WAVE, ASSIGN_FORM_WORKGROUP = 0, 1
+ASSIGN_COST_CAP = 2.0 ** 1000
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -81,6 +84,19 @@ class RangingOut(ctypes.Structure):
     _fields_ = [("dual", c_double_p), ("cost_lo", c_double_p), ("cost_hi", c_double_p),
                 ("cost_lo_at", c_int64_p), ("cost_hi_at", c_int64_p), ("rhs_lo", c_double_p), ("rhs_hi", c_double_p),
                 ("rhs_lo_at", c_int64_p), ("rhs_hi_at", c_int64_p)]
+
+
+class AssignResult(ctypes.Structure):
+    """lpg_assign_result."""
+    _fields_ = [("status", ctypes.c_int32), ("pad", ctypes.c_int32), ("steps", ctypes.c_int64),
+                ("objective", ctypes.c_double)]
+
+
+class AssignInfo(ctypes.Structure):
+    """lpg_assign_info_t."""
+    _fields_ = [("count", ctypes.c_int64), ("nr", ctypes.c_int64), ("nc", ctypes.c_int64),
+                ("tier", ctypes.c_int32), ("form", ctypes.c_int32), ("lds_bytes", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -181,6 +197,15 @@ PROTOTYPES = [
                                           c_int64_p, c_double_p]),
     ("lpg_batch_set_rhs", ctypes.c_int, [ctypes.c_void_p, c_int64_p, c_double_p]),
     ("lpg_batch_ranging", ctypes.c_int, [ctypes.c_void_p, c_int64_p, ctypes.POINTER(RangingOut)]),
+    ("lpg_assign_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_int64, ctypes.c_uint32]),
+    ("lpg_assign_load", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64]),
+    ("lpg_assign_generate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64]),
+    ("lpg_assign_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AssignResult)]),
+    ("lpg_assign_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int64_p, c_double_p, c_double_p]),
+    ("lpg_assign_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AssignInfo)]),
+    ("lpg_assign_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("lpg_assign_destroy", None, [ctypes.c_void_p]),
 ]
 
 

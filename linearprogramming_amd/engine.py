@@ -762,3 +762,85 @@ class RaggedBatchEngine(BatchEngine):
         self._check(self.lib.lpg_batch_get_basis_packed(self._b, 0, self.count, flat.ctypes.data_as(L.c_int64_p)),
                     "lpg_batch_get_basis_packed")
         return self._split(flat, lambda m, nc: (m,))
+
+
+@dataclass
+class AssignResult:
+    status: int
+    steps: int
+    objective: float
+
+    @property
+    def status_name(self) -> str:
+        return L.STATUS_NAMES.get(self.status, str(self.status))
+
+
+class AssignmentBatch:
+    """`count` assignment problems of one shape, nr x nc cost matrices with
+    nr <= nc, solved in one launch by the Hungarian method (include/lpg.h,
+    "assignment"): every row gets a distinct column, the chosen costs sum to the
+    minimum (``maximize=True``: the maximum); +inf forbids a pair."""
+
+    def __init__(self, count: int, nr: int, nc: int, device: int = 0, maximize: bool = False, lib=None):
+        self.lib = lib if lib is not None else L.load()
+        self._a = ctypes.c_void_p()
+        rc = self.lib.lpg_assign_create(ctypes.byref(self._a), device, count, nr, nc, L.ASSIGN_MAXIMIZE if maximize else 0)
+        if rc != 0:
+            raise LPGError(f"lpg_assign_create rc={rc}: {self.lib.lpg_assign_last_error(None).decode()}")
+        self.count, self.nr, self.nc, self.maximize = count, nr, nc, bool(maximize)
+
+    def close(self):
+        if self._a:
+            self.lib.lpg_assign_destroy(self._a)
+            self._a = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_assign_last_error(self._a).decode()}")
+        return rc
+
+    @property
+    def info(self) -> L.AssignInfo:
+        i = L.AssignInfo()
+        self._check(self.lib.lpg_assign_info(self._a, ctypes.byref(i)), "lpg_assign_info")
+        return i
+
+    def load(self, costs: np.ndarray, first: int = 0):
+        """costs: [n, nr, nc]; problems first .. first + n - 1."""
+        c = np.ascontiguousarray(costs, dtype=np.float64)
+        if c.ndim != 3 or c.shape[1] != self.nr or c.shape[2] != self.nc:
+            raise LPGError(f"load: costs of shape {c.shape}, want [n, {self.nr}, {self.nc}]")
+        self._check(self.lib.lpg_assign_load(self._a, first, c.shape[0], c.ctypes.data_as(L.c_double_p), self.nc),
+                    "lpg_assign_load")
+
+    def generate(self, seed: int = 20220518, range: int = 100):
+        """Problem q, entry (i, j) = floor(uniform01(seed + q, i * nc + j) * range)."""
+        self._check(self.lib.lpg_assign_generate(self._a, seed, range), "lpg_assign_generate")
+
+    def solve(self) -> list:
+        r = (L.AssignResult * self.count)()
+        self._check(self.lib.lpg_assign_solve(self._a, r), "lpg_assign_solve")
+        return [AssignResult(x.status, x.steps, x.objective) for x in r]
+
+    def get(self, first: int = 0, n: int = None):
+        """(col [n, nr] int64, u [n, nr], v [n, nc]) of problems first .. first + n - 1 after a solve."""
+        n = self.count - first if n is None else n
+        col = np.empty((n, self.nr), dtype=np.int64)
+        u = np.empty((n, self.nr), dtype=np.float64)
+        v = np.empty((n, self.nc), dtype=np.float64)
+        self._check(self.lib.lpg_assign_get(self._a, first, n, col.ctypes.data_as(L.c_int64_p),
+                                            u.ctypes.data_as(L.c_double_p), v.ctypes.data_as(L.c_double_p)),
+                    "lpg_assign_get")
+        return col, u, v

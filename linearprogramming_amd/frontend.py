@@ -812,6 +812,59 @@ def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase", r
 
 
 @dataclass
+class AssignmentSolution:
+    """solve_assignment's result for one cost matrix, in the caller's orientation."""
+    status: str                  # OPTIMAL / INFEASIBLE
+    objective: float             # NaN if infeasible
+    assignment: np.ndarray       # the column of every row; -1 for a row left out (more rows than columns) or infeasible
+    u: np.ndarray                # the row potentials [rows]
+    v: np.ndarray                # the column potentials [columns]
+    steps: int
+
+
+def solve_assignment(costs, maximize: bool = False, device: int = 0) -> list:
+    """The assignment problem of every 2-D cost matrix of ``costs`` (include/lpg.h,
+    "assignment"): the matrices of one shape together in one AssignmentBatch, one
+    launch per shape, the results in input order. min(rows, columns) pairs are
+    chosen, no row and no column twice, with the smallest (``maximize``: largest)
+    cost sum; +inf forbids a pair. A matrix with more rows than columns is solved
+    transposed and reported back in the caller's orientation: ``assignment`` is
+    still the column per row (-1 for the rows left out), u belongs to the rows
+    and v to the columns."""
+    from . import _lib as L
+    from .engine import AssignmentBatch
+    mats = []
+    for idx, c in enumerate(costs):
+        c = np.asarray(c, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+            raise FrontendError(f"solve_assignment: matrix {idx} has shape {c.shape}, want 2-D and not empty")
+        mats.append(c)
+    groups = {}
+    for idx, c in enumerate(mats):
+        tr = c.shape[0] > c.shape[1]
+        groups.setdefault((min(c.shape), max(c.shape)), []).append((idx, tr))
+    out = [None] * len(mats)
+    for (nr, nc), members in groups.items():
+        stack = np.stack([mats[idx].T if tr else mats[idx] for idx, tr in members])
+        with AssignmentBatch(len(members), nr, nc, device=device, maximize=maximize) as a:
+            a.load(stack)
+            res = a.solve()
+            col, u, v = a.get()
+        for q, (idx, tr) in enumerate(members):
+            r = res[q]
+            if tr:
+                # the batch's rows are the caller's columns: invert col, swap the potentials
+                asg = np.full(nc, -1, dtype=np.int64)
+                if r.status == L.OPTIMAL:
+                    asg[col[q]] = np.arange(nr)
+                pu, pv = v[q].copy(), u[q].copy()
+            else:
+                asg, pu, pv = col[q].copy(), u[q].copy(), v[q].copy()
+            out[idx] = AssignmentSolution(L.STATUS_NAMES[r.status], float(r.objective), asg, pu, pv, int(r.steps))
+    return out
+
+
+@dataclass
 class LPSensitivity(LPSolution):
     """sensitivity_batch's result: the LPSolution and, for an OPTIMAL model, its sensitivity report."""
     basis: list = field(default_factory=list)        # the column basic in each standard-form row, by name

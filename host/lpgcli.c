@@ -41,6 +41,13 @@
  *          in one launch; prints the shape, tier, form, the counts per status,
  *          the total steps, an FNV-1a digest of col / u / v and the time of the
  *          solve call
+ *   lpgcli --binary M N --batch B [--max] [--seed S] [--split s] [--max-nodes K] [--device D]
+ *          B 0-1 programs of M rows and N binary variables (lpg_binary_generate:
+ *          the banded planted problems, seeds S, S + 1, ...) by implicit
+ *          enumeration, 2^s sub-searches per problem, at most K nodes per
+ *          sub-search (default: to the end); prints the counts per status, the
+ *          total nodes, an FNV-1a digest of x, the info record and the time of
+ *          the solve call
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
@@ -79,11 +86,12 @@ static int usage(const char *argv0) {
                     "\t%s --synthetic M N --batch B [--dual] [--kind dense|degenerate|artificial [--big-m]] [--rule dantzig|bland] [--pivots K]"
                     " [--seed S] [--ranging]\n"
                     "\t%s --assign NR NC --batch B [--max] [--seed S] [--range R]\n"
+                    "\t%s --binary M N --batch B [--max] [--seed S] [--split s] [--max-nodes K]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
                     "\t(--dual: the dual simplex; also with --synthetic (any --gpus) and --tableau;\n"
                     "\t --kind artificial: the two-phase method)\n",
-            argv0, argv0, argv0, argv0, argv0, argv0);
+            argv0, argv0, argv0, argv0, argv0, argv0, argv0);
     return 2;
 }
 
@@ -494,6 +502,55 @@ static int run_assign(long long nr, long long nc, long long count, unsigned long
     return rc;
 }
 
+/* --binary M N --batch B: B generated 0-1 programs through lpg_binary */
+static int run_binary(long long m, long long n, long long count, unsigned long long seed, int split, long long max_nodes,
+                      int maximize, int device) {
+    lpg_binary *b = NULL;
+    if (lpg_binary_create(&b, device, count, m, n, split, maximize ? LPG_BINARY_MAXIMIZE : 0) != 0 ||
+        lpg_binary_generate(b, seed, LPG_BINARY_GEN_BANDED) != 0) {
+        fprintf(stderr, "ERROR: %s\n", lpg_binary_last_error(b));
+        lpg_binary_destroy(b);
+        return 1;
+    }
+    lpg_binary_result *res = (lpg_binary_result *)malloc((size_t)count * sizeof(lpg_binary_result));
+    int8_t *x = (int8_t *)malloc((size_t)(count * n));
+    int rc = 1;
+    if (res && x) {
+        const double t0 = now();
+        rc = lpg_binary_solve(b, max_nodes, res);
+        const double dt = now() - t0;
+        if (rc == 0) rc = lpg_binary_get(b, 0, count, x);
+        if (rc != 0) {
+            fprintf(stderr, "ERROR: %s\n", lpg_binary_last_error(b));
+            rc = 1;
+        } else {
+            long long by_status[6] = {0, 0, 0, 0, 0, 0}, nodes = 0, found = 0;
+            for (long long q = 0; q < count; q++) {
+                if (res[q].status >= 0 && res[q].status <= 5) by_status[res[q].status]++;
+                nodes += (long long)res[q].nodes;
+                found += res[q].found;
+            }
+            const uint64_t h = fnv1a(0xcbf29ce484222325ull, x, (size_t)(count * n));
+            lpg_binary_info_t info;
+            lpg_binary_info(b, &info);
+            printf("{\"m\": %lld, \"n\": %lld, \"batch\": %lld, \"sense\": \"%s\", \"split\": %d, \"rows_per_lane\": %d, "
+                   "\"tier\": \"%s\", \"lds_bytes\": %lld, \"chunk\": %d, \"launches\": %lld, \"kernel_ms\": %.6f, "
+                   "\"statuses\": {\"OPTIMAL\": %lld, \"INFEASIBLE\": %lld, \"ITER_LIMIT\": %lld}, \"found\": %lld, "
+                   "\"nodes\": %lld, \"digest\": \"%016llx\", \"seconds\": %.6f, \"problems_per_s\": %.3f, "
+                   "\"nodes_per_s\": %.3f}\n",
+                   (long long)info.m, (long long)info.n, (long long)info.count, maximize ? "max" : "min", info.split,
+                   info.rows_per_lane, info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global", (long long)info.lds_bytes,
+                   info.chunk, (long long)info.launches, info.kernel_ms, by_status[LPG_OPTIMAL], by_status[LPG_INFEASIBLE],
+                   by_status[LPG_ITER_LIMIT], found, nodes, (unsigned long long)h, dt, dt > 0 ? (double)count / dt : 0.0,
+                   dt > 0 ? (double)nodes / dt : 0.0);
+        }
+    }
+    free(res);
+    free(x);
+    lpg_binary_destroy(b);
+    return rc;
+}
+
 static char *read_all(const char *path) {
     FILE *f = fopen(path, "rb");
     if (!f) {
@@ -646,6 +703,8 @@ static int load_tableau_file(lpg_ctx **ctx, const char *path, int device) {
 
 int main(int argc, char **argv) {
     long long m = 0, n = 0, pivots = (long long)1 << 40, batch = -1, anr = 0, anc = 0, range = 100;
+    long long bm = 0, bn = 0, max_nodes = 0;
+    int binary = 0, split = 0;
     unsigned long long seed = 20220518ull;
     int kind = LPG_GEN_DENSE, rule = LPG_RULE_DANTZIG, device = 0, gpus = 1, push = 1;
     const char *file = NULL, *lpfile = NULL;
@@ -658,6 +717,14 @@ int main(int argc, char **argv) {
             assign = 1;
             anr = atoll(argv[++a]);
             anc = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--binary") && a + 2 < argc) {
+            binary = 1;
+            bm = atoll(argv[++a]);
+            bn = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--split") && a + 1 < argc) {
+            split = atoi(argv[++a]);
+        } else if (!strcmp(argv[a], "--max-nodes") && a + 1 < argc) {
+            max_nodes = atoll(argv[++a]);
         } else if (!strcmp(argv[a], "--max")) {
             maximize = 1;
         } else if (!strcmp(argv[a], "--range") && a + 1 < argc) {
@@ -696,6 +763,11 @@ int main(int argc, char **argv) {
         }
     }
     if (dual && (bigm || kind == LPG_GEN_ARTIFICIAL)) return usage(argv[0]);
+    if (binary) {
+        if (batch < 1 || assign || m || n || file || lpfile || gpus > 1 || dual || bigm || ranging) return usage(argv[0]);
+        return run_binary(bm, bn, batch, seed, split, max_nodes, maximize, device);
+    }
+    if (split || max_nodes) return usage(argv[0]);
     if (assign) {
         if (batch < 1 || m || n || file || lpfile || gpus > 1 || dual || bigm || ranging) return usage(argv[0]);
         return run_assign(anr, anc, batch, seed, range, maximize, device);

@@ -875,6 +875,157 @@ int  lpg_assign_info(const lpg_assign *a, lpg_assign_info_t *out);
 const char *lpg_assign_last_error(const lpg_assign *a);
 void lpg_assign_destroy(lpg_assign *a);                        /* NULL is a no-op */
 
+/* ---- 0-1 programs: batches of small binary programs by implicit enumeration ----
+ *
+ * The reference's README lists 0-1 integer programs by implicit enumeration
+ * among the things it meant to solve. An lpg_binary holds `count` problems of
+ * one shape, n variables (1 <= n <= LPG_BINARY_MAX_N = 64) and m rows (1 <= m
+ * <= LPG_BINARY_MAX_M = 256):
+ *
+ *     minimise (LPG_BINARY_MAXIMIZE: maximise)  c.x
+ *     subject to  a_i.x  {<=, =, >=}  b_i   (sense[i] = -1, 0, +1),  x in {0,1}^n
+ *
+ * and solves each by a depth-first walk over partial assignments with interval
+ * tests per row and a bound on the objective (lpg_binary.hip): no tableau, no
+ * division, no multiplication. Ragged batches are not provided.
+ *
+ * Data and caps. Every entry of A, b and c is a finite integer-valued fp64;
+ * for every row sum_j |a_ij| <= LPG_BINARY_SUM_CAP = 2^52 and |b_i| <=
+ * LPG_BINARY_RHS_CAP = 2^53; sum_j |c_j| <= LPG_BINARY_SUM_CAP. lpg_binary_load
+ * refuses anything else (a fraction, NaN, an infinity, a cap exceeded, a sense
+ * outside {-1, 0, 1}) with LPG_ERR_ARG before any device work; the message
+ * names the problem, the row and the entry, and nothing is loaded. -0.0 is
+ * loaded as +0.0. A maximisation negates c as it is loaded (exact) and the
+ * objective back on the way out (objective = 0.0 - inc, so a zero comes back
+ * as +0.0). Why the caps make every operation exact: every quantity below (lo,
+ * hi, comp, z, and every intermediate of their updates) is a sum of a subset
+ * of one row's entries or of the costs, each taken with a sign, so it is an
+ * integer of magnitude at most 2^52 < 2^53, and fp64 adds, subtracts and
+ * compares such integers without rounding. The order in which lanes or the
+ * host form a sum therefore cannot change a bit, and subtracting a term that
+ * was added restores the bits that stood before.
+ *
+ * The algorithm, operation for operation (numpy: tests/binary_cases.py). Per
+ * row the two-sided form L_i <= a_i.x <= U_i: `<=` gives L = -inf, U = b; `>=`
+ * gives L = b, U = +inf; `=` gives L = U = b. c is the internal, minimising
+ * cost. The preferred value of column j is p_j = (c_j < 0). A search carries:
+ * the depth d (columns 0..d-1 fixed, the rest free); the fixed values x; per
+ * level whether it is on its second value; per row lo_i and hi_i, the smallest
+ * and largest activity any completion can reach, and comp_i, the activity of
+ * the completion with every free column at its preferred value; z, the cost of
+ * that completion (the lower bound of the subtree); the incumbent (inc, inc_x),
+ * +inf and none at the start; the count `nodes`. At the root
+ *     lo_i = sum_j min(0, a_ij), hi_i = sum_j max(0, a_ij),
+ *     comp_i = sum_j p_j a_ij,   z = sum_j min(0, c_j).
+ *   1. Visit: nodes += 1. Prune if z >= inc. Else prune if any row has lo_i >
+ *      U_i or hi_i < L_i. Else, if every row has L_i <= comp_i <= U_i: the
+ *      incumbent becomes (z, x with the free columns at p), and prune.
+ *      Otherwise descend: fix column d at p_d (its first value), d += 1, visit.
+ *   2. Fix column j at value v: v = 1: lo_i += max(0, a_ij), hi_i += min(0,
+ *      a_ij); v = 0: lo_i += max(0, -a_ij), hi_i -= max(0, a_ij); and if v !=
+ *      p_j: comp_i += (v ? a_ij : -a_ij), z += |c_j|. Unfixing subtracts the
+ *      same terms (exact, so no per-level copies of the row state exist).
+ *   3. Prune (backtrack): while the deepest fixed level is on its second value,
+ *      unfix it; if no level is left the search has ended; otherwise unfix the
+ *      deepest level, fix it at the other value, mark it second, and visit.
+ * At d = n lo = hi = comp, so step 1 always ends at a leaf. A subtree is cut
+ * only when it holds no strictly better leaf, so the reported x is the first
+ * optimal point in the search order (preferred value first, column 0
+ * outermost): a property of the problem, not of the schedule. There are no
+ * fixing tests and no surrogate constraints.
+ *
+ * Split. lpg_binary_create takes `split` in 0..min(n, LPG_BINARY_MAX_SPLIT =
+ * 10): problem q is searched as 2^split independent sub-searches; sub-search k
+ * starts at depth `split` with column t < split fixed at its first value (bit
+ * t of k clear) or its second (bit t set), and never unfixes those. The
+ * sub-searches share no incumbent. Reduction (on the host, over the records
+ * copied back): sub-searches are taken in search order, i.e. ordered by (bit
+ * 0, bit 1, ..., bit split-1) of k lexicographically; the problem's inc is the
+ * smallest inc, its x that of the first sub-search in that order that reaches
+ * it, its nodes the sum, found = any. Objective and x are the same for every
+ * split; nodes is not.
+ *
+ * Budgets. A launch visits at most `chunk` nodes per sub-search (default
+ * LPG_BINARY_DEFAULT_CHUNK, env LPG_BINARY_CHUNK read at create); the whole
+ * state of a sub-search round-trips through device memory between launches.
+ * lpg_binary_solve(b, max_nodes, out) relaunches until no sub-search is
+ * running, or until every running sub-search has visited max_nodes nodes in
+ * this call (max_nodes <= 0: no budget). A sub-search is "running" while it
+ * stands before a node it has not visited; the backtrack after a visit belongs
+ * to that visit, so a search whose last visit exhausts the budget has ended.
+ * Per problem: status LPG_ITER_LIMIT while a sub-search of it is running (with
+ * the incumbent so far: found = 0 or 1, objective NaN if none), else
+ * LPG_OPTIMAL if found, else LPG_INFEASIBLE. Another call continues where the
+ * last one stopped; any number of budgeted calls ends in the same bits as one
+ * unbudgeted call. A load or generate resets every search.
+ *
+ * Generator. lpg_binary_generate(b, seed, LPG_BINARY_GEN_BANDED): problem q
+ * draws u(k) = uniform01(seed + q, k) (the engine's generator draw). With w =
+ * min(3, n) and s_i = (m > 1 && n > 3) ? floor(i (n - 3) / (m - 1)) : 0, row i
+ * has a[i][s_i + t] = floor(u(4 i + t) * 9) - 4 for t < w and zeros elsewhere;
+ * the planted point is xp_j = (u(4 m + j) < 0.5); act_i = a_i.xp; with r =
+ * u(4 i + 3): r < 0.5: sense 0, b = act; r < 0.75: sense -1, b = act + 1;
+ * else sense +1, b = act - 1. c_j = floor(u(4 m + n + j) * 19) - 9 (the
+ * caller's cost: a maximisation negates it like a loaded one). Every problem
+ * is feasible at xp.
+ *
+ * Kernel. One wave per sub-search, four waves per workgroup; row i lives on
+ * lane i mod 64 with 1, 2 or 4 rows per lane (m <= 64, 128, 256), lo, hi,
+ * comp, L, U in registers for a launch; A transposed [n][m] so a node's
+ * column read is contiguous across lanes; A^T and c in LDS where the
+ * workgroup's problems fit the 150 KiB dynamic cap (LPG_BATCH_TIER_LDS;
+ * sub-searches of one problem in a workgroup share one copy), else in device
+ * memory (LPG_BATCH_TIER_GLOBAL; env LPG_BINARY_TIER=global forces it).
+ *
+ * Every argument is checked on the host before any device work: the device is
+ * first touched by the first lpg_binary_load, _generate, _solve or _occupancy
+ * that passes its checks. The messages name the call and the first offending
+ * index; NULL handles are errors (lpg_binary_last_error(NULL): this thread's
+ * last one). One batch per host thread; not reentrant. */
+#define LPG_BINARY_MAXIMIZE        0x1u
+#define LPG_BINARY_MAX_N           64
+#define LPG_BINARY_MAX_M           256
+#define LPG_BINARY_MAX_SPLIT       10
+#define LPG_BINARY_SUM_CAP         0x1p52
+#define LPG_BINARY_RHS_CAP         0x1p53
+#define LPG_BINARY_GEN_BANDED      0
+#define LPG_BINARY_DEFAULT_CHUNK   4096
+
+typedef struct lpg_binary lpg_binary;
+typedef struct { int32_t status, found; int64_t nodes; double objective; } lpg_binary_result;
+typedef struct {
+    int64_t count, m, n;
+    int32_t split;                /* 2^split sub-searches per problem */
+    int32_t rows_per_lane;        /* 1, 2 or 4: the kernel instantiation */
+    int32_t tier;                 /* LPG_BATCH_TIER_*: where A^T and c live while a search runs */
+    int32_t chunk;                /* nodes per sub-search per launch */
+    int64_t lds_bytes;            /* dynamic LDS of one workgroup */
+    int64_t launches;             /* kernel launches of the last lpg_binary_solve */
+    double  kernel_ms;            /* device time of those launches, summed */
+} lpg_binary_info_t;
+
+/* count >= 1, 1 <= m <= 256, 1 <= n <= 64, 0 <= split <= min(n, 10), count *
+ * 2^split <= 2^31 - 1; flags 0 or LPG_BINARY_MAXIMIZE. Anything else:
+ * LPG_ERR_ARG and *out = NULL. */
+int  lpg_binary_create(lpg_binary **out, int device, int64_t count, int64_t m, int64_t n, int32_t split, uint32_t flags);
+/* Problems [first, first + np), np >= 1: A np x m rows of n entries at pitch
+ * ldA >= n, sense np x m, rhs np x m, c np x n, dense. Refused as a whole on a
+ * bad entry (see "Data and caps"). */
+int  lpg_binary_load(lpg_binary *b, int64_t first, int64_t np, const double *A, int64_t ldA, const int32_t *sense,
+                     const double *rhs, const double *c);
+int  lpg_binary_generate(lpg_binary *b, uint64_t seed, int kind);
+/* out[count] may be NULL. LPG_ERR_STATE while a problem has no data. */
+int  lpg_binary_solve(lpg_binary *b, int64_t max_nodes, lpg_binary_result *out);
+/* x of problems [first, first + np) after a solve, np x n of 0 / 1; -1
+ * throughout for a problem with nothing found. */
+int  lpg_binary_get(lpg_binary *b, int64_t first, int64_t np, int8_t *x);
+int  lpg_binary_info(const lpg_binary *b, lpg_binary_info_t *out);
+/* The waves of this batch's kernel instantiation that the device holds at once
+ * (the occupancy query times the compute units times four). */
+int  lpg_binary_occupancy(lpg_binary *b, int64_t *resident_waves);
+const char *lpg_binary_last_error(const lpg_binary *b);
+void lpg_binary_destroy(lpg_binary *b);                        /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

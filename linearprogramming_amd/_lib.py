@@ -32,11 +32,16 @@ BATCH_MAX_CUTS = 1024
 ASSIGN_MAXIMIZE = 0x1
 ASSIGN_FORM_WAVE, ASSIGN_FORM_WORKGROUP = 0, 1
 ASSIGN_COST_CAP = 2.0 ** 1000
+BINARY_MAXIMIZE = 0x1
+BINARY_MAX_N, BINARY_MAX_M, BINARY_MAX_SPLIT = 64, 256, 10
+BINARY_SUM_CAP, BINARY_RHS_CAP = 2.0 ** 52, 2.0 ** 53
+BINARY_GEN_BANDED = 0
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
 c_int8_p = ctypes.POINTER(ctypes.c_int8)
+c_int32_p = ctypes.POINTER(ctypes.c_int32)
 
 
 class Result(ctypes.Structure):
@@ -96,6 +101,20 @@ class AssignInfo(ctypes.Structure):
     """lpg_assign_info_t."""
     _fields_ = [("count", ctypes.c_int64), ("nr", ctypes.c_int64), ("nc", ctypes.c_int64),
                 ("tier", ctypes.c_int32), ("form", ctypes.c_int32), ("lds_bytes", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
+class BinaryResult(ctypes.Structure):
+    """lpg_binary_result."""
+    _fields_ = [("status", ctypes.c_int32), ("found", ctypes.c_int32), ("nodes", ctypes.c_int64),
+                ("objective", ctypes.c_double)]
+
+
+class BinaryInfo(ctypes.Structure):
+    """lpg_binary_info_t."""
+    _fields_ = [("count", ctypes.c_int64), ("m", ctypes.c_int64), ("n", ctypes.c_int64),
+                ("split", ctypes.c_int32), ("rows_per_lane", ctypes.c_int32), ("tier", ctypes.c_int32),
+                ("chunk", ctypes.c_int32), ("lds_bytes", ctypes.c_int64), ("launches", ctypes.c_int64),
                 ("kernel_ms", ctypes.c_double)]
 
 
@@ -206,6 +225,17 @@ PROTOTYPES = [
     ("lpg_assign_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AssignInfo)]),
     ("lpg_assign_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
     ("lpg_assign_destroy", None, [ctypes.c_void_p]),
+    ("lpg_binary_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32]),
+    ("lpg_binary_load", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64,
+                                       c_int32_p, c_double_p, c_double_p]),
+    ("lpg_binary_generate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int]),
+    ("lpg_binary_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(BinaryResult)]),
+    ("lpg_binary_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_int8_p]),
+    ("lpg_binary_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BinaryInfo)]),
+    ("lpg_binary_occupancy", ctypes.c_int, [ctypes.c_void_p, c_int64_p]),
+    ("lpg_binary_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("lpg_binary_destroy", None, [ctypes.c_void_p]),
 ]
 
 

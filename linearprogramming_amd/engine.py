@@ -844,3 +844,97 @@ class AssignmentBatch:
                                             u.ctypes.data_as(L.c_double_p), v.ctypes.data_as(L.c_double_p)),
                     "lpg_assign_get")
         return col, u, v
+
+
+@dataclass
+class BinaryResult:
+    status: int
+    found: int
+    nodes: int
+    objective: float
+
+    @property
+    def status_name(self) -> str:
+        return L.STATUS_NAMES.get(self.status, str(self.status))
+
+
+class BinaryBatch:
+    """`count` 0-1 programs of one shape, m rows and n <= 64 binary variables,
+    solved by implicit enumeration on the device (include/lpg.h, "0-1
+    programs"): minimise (``maximize=True``: maximise) c.x subject to a_i.x
+    {<=, =, >=} b_i on integer data; 2^split independent sub-searches per problem."""
+
+    def __init__(self, count: int, m: int, n: int, split: int = 0, maximize: bool = False, device: int = 0, lib=None):
+        self.lib = lib if lib is not None else L.load()
+        self._b = ctypes.c_void_p()
+        rc = self.lib.lpg_binary_create(ctypes.byref(self._b), device, count, m, n, split,
+                                        L.BINARY_MAXIMIZE if maximize else 0)
+        if rc != 0:
+            raise LPGError(f"lpg_binary_create rc={rc}: {self.lib.lpg_binary_last_error(None).decode()}")
+        self.count, self.m, self.n, self.split, self.maximize = count, m, n, split, bool(maximize)
+
+    def close(self):
+        if self._b:
+            self.lib.lpg_binary_destroy(self._b)
+            self._b = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_binary_last_error(self._b).decode()}")
+        return rc
+
+    @property
+    def info(self) -> L.BinaryInfo:
+        i = L.BinaryInfo()
+        self._check(self.lib.lpg_binary_info(self._b, ctypes.byref(i)), "lpg_binary_info")
+        return i
+
+    @property
+    def resident_waves(self) -> int:
+        """The waves of this batch's kernel that the device holds at once (the occupancy query)."""
+        w = ctypes.c_int64()
+        self._check(self.lib.lpg_binary_occupancy(self._b, ctypes.byref(w)), "lpg_binary_occupancy")
+        return int(w.value)
+
+    def load(self, A, sense, rhs, c, first: int = 0):
+        """A [k, m, n], sense [k, m] of -1 / 0 / +1, rhs [k, m], c [k, n]: problems first .. first + k - 1."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        sense = np.ascontiguousarray(sense, dtype=np.int32)
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        k = A.shape[0] if A.ndim == 3 else -1
+        if A.shape != (k, self.m, self.n) or sense.shape != (k, self.m) or rhs.shape != (k, self.m) or c.shape != (k, self.n):
+            raise LPGError(f"load: shapes {A.shape}, {sense.shape}, {rhs.shape}, {c.shape}, want [k, {self.m}, {self.n}], "
+                           f"[k, {self.m}], [k, {self.m}], [k, {self.n}]")
+        self._check(self.lib.lpg_binary_load(self._b, first, k, A.ctypes.data_as(L.c_double_p), self.n,
+                                             sense.ctypes.data_as(L.c_int32_p), rhs.ctypes.data_as(L.c_double_p),
+                                             c.ctypes.data_as(L.c_double_p)), "lpg_binary_load")
+
+    def generate(self, seed: int = 20220518, kind: int = L.BINARY_GEN_BANDED):
+        """The banded planted problems of include/lpg.h ("Generator"), problem q from seed + q."""
+        self._check(self.lib.lpg_binary_generate(self._b, seed, kind), "lpg_binary_generate")
+
+    def solve(self, max_nodes: int = 0) -> list:
+        """Continues every search, by at most max_nodes nodes per sub-search (0: to the end)."""
+        r = (L.BinaryResult * self.count)()
+        self._check(self.lib.lpg_binary_solve(self._b, max_nodes, r), "lpg_binary_solve")
+        return [BinaryResult(x.status, x.found, x.nodes, x.objective) for x in r]
+
+    def get(self, first: int = 0, n: int = None) -> np.ndarray:
+        """x [n, self.n] int8 of problems first .. first + n - 1 after a solve; -1 throughout where nothing was found."""
+        n = self.count - first if n is None else n
+        x = np.empty((n, self.n), dtype=np.int8)
+        self._check(self.lib.lpg_binary_get(self._b, first, n, x.ctypes.data_as(L.c_int8_p)), "lpg_binary_get")
+        return x

@@ -29,6 +29,10 @@ the reference binary's transcripts). Stages, each citing what it restates:
                    first solved, the others restated from its tableau on the
                    device and re-optimised by the dual simplex
                    (BatchEngine.scenario, DESIGN.md §3.7, "Scenarios")
+* ``solve_binary``  0-1 programs by implicit enumeration (the reference's
+                   wish-list, README), one BinaryBatch per shape; and
+                   ``solve_binary_text`` for the reference's model text with
+                   every variable 0-1 ("0-1 programs")
 
 The variable table mirrors hashTable.c (PutVarItem replaces an existing key in
 place; GetVarItems walks buckets in hash order, VarHash hashTable.c:148-167).
@@ -862,6 +866,144 @@ def solve_assignment(costs, maximize: bool = False, device: int = 0) -> list:
                 asg, pu, pv = col[q].copy(), u[q].copy(), v[q].copy()
             out[idx] = AssignmentSolution(L.STATUS_NAMES[r.status], float(r.objective), asg, pu, pv, int(r.steps))
     return out
+
+
+@dataclass
+class BinarySolution:
+    """solve_binary's result for one 0-1 program, in the caller's column order."""
+    status: str                  # OPTIMAL, INFEASIBLE, or ITER_LIMIT (max_nodes reached: the incumbent so far)
+    objective: float             # NaN when no point was found
+    x: np.ndarray                # int8 0 / 1; -1 throughout when no point was found
+    nodes: int
+    names: list = None           # solve_binary_text: the variable of every entry of x
+
+
+def binary_order(c, order) -> np.ndarray:
+    """The columns in the order the device is given them: "cost": by descending |c_j|, ties to the smaller j (the
+    textbook's ordering: the bound bites early); None: as given."""
+    c = np.asarray(c, dtype=np.float64)
+    if order is None:
+        return np.arange(len(c))
+    if order != "cost":
+        raise FrontendError(f"solve_binary: order {order!r} unknown (\"cost\" or None)")
+    return np.array(sorted(range(len(c)), key=lambda j: (-abs(c[j]), j)), dtype=np.int64)
+
+
+def binary_split(count: int, m: int, n: int, maximize: bool = False, device: int = 0) -> int:
+    """The smallest split that gives a batch of `count` problems at least as many waves as the device holds at
+    once (BinaryBatch.resident_waves: the occupancy query for the instantiation that split selects)."""
+    from . import _lib as L
+    from .engine import BinaryBatch
+    top = min(n, L.BINARY_MAX_SPLIT)
+    for s in range(top + 1):
+        with BinaryBatch(count, m, n, split=s, maximize=maximize, device=device) as b:
+            if (count << s) >= b.resident_waves:
+                return s
+    return top
+
+
+def _binary_batch(A, sense, rhs, c, maximize, split, max_nodes, device):
+    """One batch of one shape on the device: (status, found, nodes, objective) per problem and x [count, n]."""
+    from .engine import BinaryBatch
+    count, m, n = A.shape
+    if split is None:
+        split = binary_split(count, m, n, maximize, device)
+    with BinaryBatch(count, m, n, split=split, maximize=maximize, device=device) as b:
+        b.load(A, sense, rhs, c)
+        res = b.solve(max_nodes)
+        return [(r.status, r.found, r.nodes, r.objective) for r in res], b.get()
+
+
+def solve_binary(models, maximize: bool = False, split=None, order="cost", max_nodes: int = 0, device: int = 0) -> list:
+    """The 0-1 program of every (A, sense, rhs, c) of ``models`` (include/lpg.h, "0-1 programs"): minimise
+    (``maximize``: maximise) c.x subject to a_i.x {<=, =, >=} b_i (sense -1, 0, +1), x binary, on integer data.
+    The models of one shape run together in one BinaryBatch; the results come back in input order, x in the
+    caller's column order whatever ``order`` presents to the device."""
+    from . import _lib as L
+    items = []
+    for idx, mod in enumerate(models):
+        if len(mod) != 4:
+            raise FrontendError(f"solve_binary: model {idx} is not a tuple (A, sense, rhs, c)")
+        A, sense, rhs, c = (np.asarray(a) for a in mod)
+        if A.ndim != 2 or A.shape[0] < 1 or A.shape[1] < 1 or sense.shape != (A.shape[0],) or rhs.shape != (A.shape[0],) \
+                or c.shape != (A.shape[1],):
+            raise FrontendError(f"solve_binary: model {idx} has shapes {A.shape}, {sense.shape}, {rhs.shape}, {c.shape}, "
+                                "want [m, n], [m], [m], [n]")
+        perm = binary_order(c, order)
+        items.append((np.asarray(A, dtype=np.float64)[:, perm], sense.astype(np.int32), rhs.astype(np.float64),
+                      np.asarray(c, dtype=np.float64)[perm], perm))
+    groups = {}
+    for idx, it in enumerate(items):
+        groups.setdefault(it[0].shape, []).append(idx)
+    out = [None] * len(items)
+    for (m, n), members in groups.items():
+        stack = [np.stack([items[idx][f] for idx in members]) for f in range(4)]
+        res, x = _binary_batch(stack[0], stack[1], stack[2], stack[3], maximize, split, max_nodes, device)
+        for q, idx in enumerate(members):
+            xo = np.full(n, -1, dtype=np.int8)
+            xo[items[idx][4]] = x[q]
+            out[idx] = BinarySolution(L.STATUS_NAMES[res[q][0]], float(res[q][3]), xo, int(res[q][2]))
+    return out
+
+
+def binary_model(text: str):
+    """The reference's model text as a 0-1 program on integers: (A, sense, rhs, c, maximize, names, scale,
+    offset). Every variable is binary: a sign-constraint line x >= 0 is accepted and ignored, x <= 0 refused.
+    Each row and the objective are scaled to integers by the least common multiple of their denominators
+    (`scale`: the objective's; the model's own objective is c.x / scale + offset). A strict < or > on the
+    integer row becomes <= b - 1 or >= b + 1."""
+    from functools import cmp_to_key
+    m = lp_trans(parse(text))
+    for it in m.vars.items.values():
+        if it.relation < 0:
+            raise FrontendError(f"solve_binary_text: {it.name} <= 0 contradicts a 0-1 variable")
+    names = sorted(m.vars.items, key=cmp_to_key(_varcmp))
+    col = {v: j for j, v in enumerate(names)}
+
+    def lcm_of(values):
+        d = 1
+        for v in values:
+            d = d * v.denominator // gcd(d, v.denominator)
+        return d
+
+    A = np.zeros((len(m.rows), len(names)))
+    sense, rhs = np.zeros(len(m.rows), dtype=np.int32), np.zeros(len(m.rows))
+    for i, st in enumerate(m.rows):
+        coefs = [(t.var, t.coef.value()) for t in st.left]
+        b = st.right[0].coef.value()
+        d = lcm_of([v for _, v in coefs] + [b])
+        for var, v in coefs:
+            A[i, col[var]] = float(v * d)
+        bi = int(b * d)
+        if st.relation == 3:
+            sense[i] = 0
+        elif st.relation < 0:
+            sense[i], bi = -1, (bi - 1 if st.relation == -1 else bi)
+        else:
+            sense[i], bi = 1, (bi + 1 if st.relation == 1 else bi)
+        rhs[i] = float(bi)
+    obj = [(t.var, t.coef.value()) for t in m.objective]
+    scale = lcm_of([v for var, v in obj if var])
+    c = np.zeros(len(names))
+    offset = Fraction(0)
+    for var, v in obj:
+        if var:
+            c[col[var]] = float(v * scale)
+        else:
+            offset += v
+    return A, sense, rhs, c, m.otype == 1, names, scale, offset
+
+
+def solve_binary_text(text: str, split=None, order="cost", max_nodes: int = 0, device: int = 0) -> BinarySolution:
+    """The reference's model text with every variable 0-1 (binary_model), solved on the device; the objective is
+    reported in the model's own scale."""
+    A, sense, rhs, c, maximize, names, scale, offset = binary_model(text)
+    sol = solve_binary([(A, sense, rhs, c)], maximize=maximize, split=split, order=order, max_nodes=max_nodes,
+                       device=device)[0]
+    if sol.objective == sol.objective:
+        sol.objective = float(Fraction(int(sol.objective), scale) + offset)
+    sol.names = names
+    return sol
 
 
 @dataclass

@@ -48,6 +48,14 @@
  *          sub-search (default: to the end); prints the counts per status, the
  *          total nodes, an FNV-1a digest of x, the info record and the time of
  *          the solve call
+ *   lpgcli --transport NR NC --batch B [--max] [--seed S] [--range R] [--qmax Q] [--start nw] [--rule bland] [--device D]
+ *          B transportation problems of NR sources and NC sinks
+ *          (lpg_transport_generate: costs in 0..R-1, default 100, amounts in
+ *          1..Q, default 9, seeds S, S + 1, ...) by the tableau method from the
+ *          least-cost (--start nw: northwest-corner) start, at most 50 (NR + NC)
+ *          iterations; prints the info record, the counts per status, the total
+ *          iterations, an FNV-1a digest of x / u / v / basis and the time of the
+ *          solve call
  *
  * FILE: "m ncols" then m+1 rows of ncols numbers ([b | a_1..a_N], objective
  * row last, d_j = z_j - c_j), then m basic columns (1-based).
@@ -87,11 +95,12 @@ static int usage(const char *argv0) {
                     " [--seed S] [--ranging]\n"
                     "\t%s --assign NR NC --batch B [--max] [--seed S] [--range R]\n"
                     "\t%s --binary M N --batch B [--max] [--seed S] [--split s] [--max-nodes K]\n"
+                    "\t%s --transport NR NC --batch B [--max] [--seed S] [--range R] [--qmax Q] [--start nw] [--rule bland]\n"
                     "\t%s --tableau FILE [--rule dantzig|bland] [--pivots K]\n"
                     "\t%s --lp MODEL [--big-m | --dual] [--rule dantzig|bland]\n\t%s --lp-dump MODEL [--dual]\n"
                     "\t(--dual: the dual simplex; also with --synthetic (any --gpus) and --tableau;\n"
                     "\t --kind artificial: the two-phase method)\n",
-            argv0, argv0, argv0, argv0, argv0, argv0, argv0);
+            argv0, argv0, argv0, argv0, argv0, argv0, argv0, argv0);
     return 2;
 }
 
@@ -502,6 +511,66 @@ static int run_assign(long long nr, long long nc, long long count, unsigned long
     return rc;
 }
 
+/* --transport NR NC --batch B: B generated transportation problems through lpg_transport */
+static int run_transport(long long nr, long long nc, long long count, unsigned long long seed, long long range,
+                         long long qmax, int maximize, int northwest, int rule, int device) {
+    lpg_transport *t = NULL;
+    const uint32_t flags = (maximize ? LPG_TRANSPORT_MAXIMIZE : 0) |
+                           (northwest ? LPG_TRANSPORT_START_NORTHWEST : LPG_TRANSPORT_START_LEAST_COST);
+    if (lpg_transport_create(&t, device, count, nr, nc, flags) != 0 || lpg_transport_generate(t, seed, range, qmax) != 0) {
+        fprintf(stderr, "ERROR: %s\n", lpg_transport_last_error(t));
+        lpg_transport_destroy(t);
+        return 1;
+    }
+    const long long nb = nr + nc - 1;
+    lpg_transport_result *res = (lpg_transport_result *)malloc((size_t)count * sizeof(lpg_transport_result));
+    double *x = (double *)malloc((size_t)(count * nr * nc) * sizeof(double));
+    double *u = (double *)malloc((size_t)(count * nr) * sizeof(double));
+    double *v = (double *)malloc((size_t)(count * nc) * sizeof(double));
+    int64_t *basis = (int64_t *)malloc((size_t)(count * nb) * sizeof(int64_t));
+    int rc = 1;
+    if (res && x && u && v && basis) {
+        const double t0 = now();
+        rc = lpg_transport_solve(t, 50 * (nr + nc), rule, res);
+        const double dt = now() - t0;
+        if (rc == 0) rc = lpg_transport_get(t, 0, count, x, u, v, basis);
+        if (rc != 0) {
+            fprintf(stderr, "ERROR: %s\n", lpg_transport_last_error(t));
+            rc = 1;
+        } else {
+            long long by_status[6] = {0, 0, 0, 0, 0, 0}, iters = 0;
+            for (long long q = 0; q < count; q++) {
+                if (res[q].status >= 0 && res[q].status <= 5) by_status[res[q].status]++;
+                iters += (long long)res[q].iterations;
+            }
+            uint64_t h = 0xcbf29ce484222325ull;
+            h = fnv1a(h, x, (size_t)(count * nr * nc) * 8);
+            h = fnv1a(h, u, (size_t)(count * nr) * 8);
+            h = fnv1a(h, v, (size_t)(count * nc) * 8);
+            h = fnv1a(h, basis, (size_t)(count * nb) * 8);
+            lpg_transport_info_t info;
+            lpg_transport_info(t, &info);
+            printf("{\"nr\": %lld, \"nc\": %lld, \"batch\": %lld, \"sense\": \"%s\", \"start\": \"%s\", \"rule\": \"%s\", "
+                   "\"tier\": \"%s\", \"form\": \"%s\", \"lds_bytes\": %lld, \"chunk\": %d, \"launches\": %lld, "
+                   "\"kernel_ms\": %.6f, \"statuses\": {\"OPTIMAL\": %lld, \"ITER_LIMIT\": %lld}, \"iterations\": %lld, "
+                   "\"digest\": \"%016llx\", \"seconds\": %.6f, \"problems_per_s\": %.3f}\n",
+                   (long long)info.nr, (long long)info.nc, (long long)info.count, maximize ? "max" : "min",
+                   northwest ? "northwest" : "least_cost", rule == LPG_RULE_BLAND ? "bland" : "dantzig",
+                   info.tier == LPG_BATCH_TIER_LDS ? "lds" : "global",
+                   info.form == LPG_TRANSPORT_FORM_WAVE ? "wave" : "workgroup", (long long)info.lds_bytes, info.chunk,
+                   (long long)info.launches, info.kernel_ms, by_status[LPG_OPTIMAL], by_status[LPG_ITER_LIMIT], iters,
+                   (unsigned long long)h, dt, dt > 0 ? (double)count / dt : 0.0);
+        }
+    }
+    free(res);
+    free(x);
+    free(u);
+    free(v);
+    free(basis);
+    lpg_transport_destroy(t);
+    return rc;
+}
+
 /* --binary M N --batch B: B generated 0-1 programs through lpg_binary */
 static int run_binary(long long m, long long n, long long count, unsigned long long seed, int split, long long max_nodes,
                       int maximize, int device) {
@@ -704,7 +773,8 @@ static int load_tableau_file(lpg_ctx **ctx, const char *path, int device) {
 int main(int argc, char **argv) {
     long long m = 0, n = 0, pivots = (long long)1 << 40, batch = -1, anr = 0, anc = 0, range = 100;
     long long bm = 0, bn = 0, max_nodes = 0;
-    int binary = 0, split = 0;
+    long long tnr = 0, tnc = 0, qmax = 9;
+    int binary = 0, split = 0, transport = 0, northwest = 0;
     unsigned long long seed = 20220518ull;
     int kind = LPG_GEN_DENSE, rule = LPG_RULE_DANTZIG, device = 0, gpus = 1, push = 1;
     const char *file = NULL, *lpfile = NULL;
@@ -717,6 +787,14 @@ int main(int argc, char **argv) {
             assign = 1;
             anr = atoll(argv[++a]);
             anc = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--transport") && a + 2 < argc) {
+            transport = 1;
+            tnr = atoll(argv[++a]);
+            tnc = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--qmax") && a + 1 < argc) {
+            qmax = atoll(argv[++a]);
+        } else if (!strcmp(argv[a], "--start") && a + 1 < argc) {
+            northwest = !strcmp(argv[++a], "nw");
         } else if (!strcmp(argv[a], "--binary") && a + 2 < argc) {
             binary = 1;
             bm = atoll(argv[++a]);
@@ -763,6 +841,13 @@ int main(int argc, char **argv) {
         }
     }
     if (dual && (bigm || kind == LPG_GEN_ARTIFICIAL)) return usage(argv[0]);
+    if (transport) {
+        if (batch < 1 || binary || assign || m || n || file || lpfile || gpus > 1 || dual || bigm || ranging || split ||
+            max_nodes)
+            return usage(argv[0]);
+        return run_transport(tnr, tnc, batch, seed, range, qmax, maximize, northwest, rule, device);
+    }
+    if (northwest || qmax != 9) return usage(argv[0]);
     if (binary) {
         if (batch < 1 || assign || m || n || file || lpfile || gpus > 1 || dual || bigm || ranging) return usage(argv[0]);
         return run_binary(bm, bn, batch, seed, split, max_nodes, maximize, device);

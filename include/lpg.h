@@ -1026,6 +1026,158 @@ int  lpg_binary_occupancy(lpg_binary *b, int64_t *resident_waves);
 const char *lpg_binary_last_error(const lpg_binary *b);
 void lpg_binary_destroy(lpg_binary *b);                        /* NULL is a no-op */
 
+/* ---- transportation: batches of balanced transportation problems ----
+ *
+ * Between duality and integer programming the textbook course behind the
+ * reference's README has the transportation problem, solved by the tableau
+ * method: a start by the northwest-corner or least-cost rule, potentials u, v
+ * (MODI) with a pricing of the non-basic cells, and a closed-loop adjustment
+ * of the flows. Stated as an LP a problem of nr sources and nc sinks has nr +
+ * nc equality rows over nr * nc columns at a maximally degenerate vertex. An
+ * lpg_transport holds `count` problems of one shape instead, 1 <= nr, 1 <= nc,
+ * nr + nc <= LPG_TRANSPORT_MAX_NODES = 4096:
+ *
+ *     minimise (LPG_TRANSPORT_MAXIMIZE: maximise)  sum_ij c_ij x_ij
+ *     subject to  sum_j x_ij = s_i,  sum_i x_ij = d_j,  x >= 0
+ *
+ * and solves them by that method (lpg_transport.hip). Unbalanced problems,
+ * forbidden routes and ragged batches are not provided here (frontend.py
+ * solve_transportation handles the first two).
+ *
+ * Data and caps. Every cost, supply and demand is a finite integer-valued fp64
+ * with |c_ij| <= LPG_TRANSPORT_COST_CAP = 2^40, s_i >= 0, d_j >= 0, sum s = sum
+ * d <= 2^53 and max |c| * sum s <= 2^53 (checked in integer arithmetic).
+ * lpg_transport_load refuses anything else with LPG_ERR_ARG before any device
+ * work; the message names the problem and the entry (for an unbalanced problem
+ * both sums), and nothing is loaded. Zero supplies and demands are allowed. A
+ * minimisation loads c + 0.0 and a maximisation 0.0 - c (exact, and no -0.0
+ * inside); a maximisation reports 0.0 - u, 0.0 - v and 0.0 - objective. Why
+ * the caps make every operation exact: a potential is an alternating sum of at
+ * most nr + nc - 1 < 2^12 costs along a tree path, so below 2^52 in magnitude;
+ * a reduced cost is a cost less two potentials, below 2^53; a flow is at most
+ * sum s; the objective is at most max |c| * sum s. fp64 adds, subtracts,
+ * multiplies and compares such integers without rounding, so no order of
+ * evaluation can change a bit.
+ *
+ * The method, operation for operation (numpy: tests/transport_cases.py). Cell
+ * (i, j) has index i * nc + j. The basis is a list of exactly nr + nc - 1
+ * cells with their flows, a spanning tree of the bipartite graph of rows and
+ * columns; a cell with flow 0 may be basic.
+ *   Start, LPG_TRANSPORT_START_NORTHWEST. Begin at (0, 0) with rs = s_0, rd =
+ *     d_0. nr + nc - 1 times: x = min(rs, rd); the cell becomes basic with
+ *     flow x; rs -= x, rd -= x; after the last cell stop; otherwise if rs == 0
+ *     and i < nr - 1 move down (i += 1, rs = s_i), else move right (j += 1,
+ *     rd = d_j).
+ *   Start, LPG_TRANSPORT_START_LEAST_COST (the default). All rows and columns
+ *     are open, rs = s, rd = d. nr + nc - 1 times: take the open cell (row and
+ *     column open) of smallest cost, ties to the smallest cell index; x =
+ *     min(rs_i, rd_j); the cell becomes basic with flow x; rs_i -= x, rd_j -=
+ *     x; after the last cell stop; otherwise close exactly one line: the row
+ *     if rs_i == 0 and (rd_j != 0 or more than one row is open), else the
+ *     column. (On balanced data an open cell always exists.)
+ *   Iteration.
+ *   1. Potentials. u_0 = 0. Along the tree a known row gives v_j = c_ij - u_i
+ *      over a basic cell, a known column u_i = c_ij - v_j. The tree path from
+ *      row 0 is unique, so the order of discovery does not matter.
+ *   2. Pricing. delta_ij = (c_ij - u_i) - v_j over all cells. LPG_RULE_DANTZIG
+ *      takes the smallest delta, ties to the smallest cell index;
+ *      LPG_RULE_BLAND the smallest cell index with delta < 0. No delta < 0:
+ *      the problem is LPG_OPTIMAL. Else, if the call has applied max_iters
+ *      iterations to this problem: LPG_ITER_LIMIT, the state stays and a later
+ *      call continues from it.
+ *   3. Closed loop. Take the tree path from column j* to row i* of the
+ *      entering cell; its 1st, 3rd, ... cells are the minus cells, the others
+ *      the plus cells. theta is the smallest flow on a minus cell; the leaving
+ *      cell is the minus cell with flow == theta and the smallest cell index.
+ *      Minus cells lose theta, plus cells gain it; the entering cell takes the
+ *      leaving cell's slot with flow theta. iterations += 1.
+ * These rules do not exclude cycling at a degenerate vertex, so
+ * lpg_transport_solve takes max_iters >= 1 and has no unbounded form.
+ *
+ * Per problem: status (LPG_OPTIMAL, LPG_ITER_LIMIT; LPG_NUMERIC would mean the
+ * cell list is no tree, which the method cannot produce); iterations;
+ * objective = sum c x in the caller's sense; the dense flows x[nr][nc]; u[nr]
+ * and v[nc] of the basis as it stands; the basic cell indices ascending.
+ * After LPG_OPTIMAL the certificate holds exactly: u_i + v_j <= c_ij (>= for a
+ * maximisation) with equality on basic cells.
+ *
+ * Budgets. A launch applies at most `chunk` iterations per problem (default
+ * LPG_TRANSPORT_DEFAULT_CHUNK, env LPG_TRANSPORT_CHUNK read at create) and the
+ * host relaunches while a problem is unfinished and the call has budget left.
+ * What crosses a launch is the cell list with its flows, the iteration count
+ * and the status; potentials and tree are rebuilt from the cell list in every
+ * iteration. Any sequence of budgets ends in the bits of one sufficient call.
+ * A load or generate resets the problems it writes.
+ *
+ * Generator. lpg_transport_generate(t, seed, range, qmax): problem q draws
+ * U(k) = uniform01(seed + q, k) (the engine's generator draw, oracle
+ * lpo_uniform): c_ij = floor(U(i nc + j) range), s_i = 1 + floor(U(nr nc + i)
+ * qmax), d_j = 1 + floor(U(nr nc + nr + j) qmax); the side with the smaller
+ * sum gets the difference added to its last entry. range in 1..2^40 + 1, qmax
+ * >= 1, (range - 1) max(nr, nc) qmax <= 2^53.
+ *
+ * Forms. nr + nc <= 64: one wave per problem, four problems per workgroup, no
+ * workgroup barrier (the wave form). Else, or with env
+ * LPG_TRANSPORT_FORM=workgroup, one workgroup of 256 threads per problem. Both
+ * run one kernel body: 32 bytes of LDS per node (potential, flow, cell,
+ * predecessor, depth, loop sign), the cells strided over the problem's threads
+ * for the start and the pricing, the argmin by the DPP reductions over the
+ * total-order key of the value and the cell index. C sits in LDS where it fits
+ * the 150 KiB dynamic cap beside the node state (LPG_BATCH_TIER_LDS, up to 134
+ * x 134), else in device memory, read coalesced (LPG_BATCH_TIER_GLOBAL; env
+ * LPG_TRANSPORT_TIER=global forces it, and with it the workgroup form). Every
+ * form and tier computes the same bits. The least-cost start is nr + nc - 1
+ * sweeps over C inside the first launch.
+ *
+ * Every argument is checked on the host before any device work: the device is
+ * first touched by the first lpg_transport_load, _generate or _solve that
+ * passes its checks. The messages name the call and the first offending
+ * index; NULL handles are errors (lpg_transport_last_error(NULL): this
+ * thread's last one). One batch per host thread; not reentrant. */
+#define LPG_TRANSPORT_MAXIMIZE          0x1u
+#define LPG_TRANSPORT_START_LEAST_COST  0x0u
+#define LPG_TRANSPORT_START_NORTHWEST   0x2u
+#define LPG_TRANSPORT_FORM_WAVE         0
+#define LPG_TRANSPORT_FORM_WORKGROUP    1
+#define LPG_TRANSPORT_MAX_NODES         4096
+#define LPG_TRANSPORT_COST_CAP          0x1p40
+#define LPG_TRANSPORT_DEFAULT_CHUNK     1024
+
+typedef struct lpg_transport lpg_transport;
+/* started: 0 until the problem's start has been made (the library's own) */
+typedef struct { int32_t status, started; int64_t iterations; double objective; } lpg_transport_result;
+typedef struct {
+    int64_t count, nr, nc;
+    int32_t tier;                 /* LPG_BATCH_TIER_*: where C lives while a problem runs */
+    int32_t form;                 /* LPG_TRANSPORT_FORM_* */
+    int32_t start;                /* LPG_TRANSPORT_START_* */
+    int32_t chunk;                /* iterations per problem per launch */
+    int64_t lds_bytes;            /* dynamic LDS of one workgroup */
+    int64_t launches;             /* kernel launches of the last lpg_transport_solve */
+    double  kernel_ms;            /* device time of those launches, summed */
+} lpg_transport_info_t;
+
+/* count >= 1 problems of nr x nc, nr >= 1, nc >= 1, nr + nc <= 4096, count *
+ * nr * nc <= 2^31 - 1; flags: LPG_TRANSPORT_MAXIMIZE, LPG_TRANSPORT_START_*.
+ * Anything else: LPG_ERR_ARG and *out = NULL. */
+int  lpg_transport_create(lpg_transport **out, int device, int64_t count, int64_t nr, int64_t nc, uint32_t flags);
+/* Problems [first, first + n), n >= 1: n x nr rows of nc costs at pitch ld >=
+ * nc, supply n x nr, demand n x nc, dense. Refused as a whole (nothing is
+ * loaded) on a bad entry, see "Data and caps". */
+int  lpg_transport_load(lpg_transport *t, int64_t first, int64_t n, const double *costs, int64_t ld, const double *supply,
+                        const double *demand);
+int  lpg_transport_generate(lpg_transport *t, uint64_t seed, int64_t range, int64_t qmax);
+/* Continues every problem that is not LPG_OPTIMAL by at most max_iters >= 1
+ * iterations; rule: LPG_RULE_DANTZIG or LPG_RULE_BLAND; out[count] may be
+ * NULL. LPG_ERR_STATE while a problem has no data. */
+int  lpg_transport_solve(lpg_transport *t, int64_t max_iters, int rule, lpg_transport_result *out);
+/* Of problems [first, first + n) after a solve: x n x nr x nc, u n x nr, v n x
+ * nc, basis n x (nr + nc - 1), dense; each may be NULL, not all four. */
+int  lpg_transport_get(lpg_transport *t, int64_t first, int64_t n, double *x, double *u, double *v, int64_t *basis);
+int  lpg_transport_info(const lpg_transport *t, lpg_transport_info_t *out);
+const char *lpg_transport_last_error(const lpg_transport *t);
+void lpg_transport_destroy(lpg_transport *t);                  /* NULL is a no-op */
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,11 @@ BINARY_MAXIMIZE = 0x1
 BINARY_MAX_N, BINARY_MAX_M, BINARY_MAX_SPLIT = 64, 256, 10
 BINARY_SUM_CAP, BINARY_RHS_CAP = 2.0 ** 52, 2.0 ** 53
 BINARY_GEN_BANDED = 0
+TRANSPORT_MAXIMIZE = 0x1
+TRANSPORT_START_LEAST_COST, TRANSPORT_START_NORTHWEST = 0x0, 0x2
+TRANSPORT_FORM_WAVE, TRANSPORT_FORM_WORKGROUP = 0, 1
+TRANSPORT_MAX_NODES = 4096
+TRANSPORT_COST_CAP = 2.0 ** 40
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -116,6 +121,19 @@ class BinaryInfo(ctypes.Structure):
                 ("split", ctypes.c_int32), ("rows_per_lane", ctypes.c_int32), ("tier", ctypes.c_int32),
                 ("chunk", ctypes.c_int32), ("lds_bytes", ctypes.c_int64), ("launches", ctypes.c_int64),
                 ("kernel_ms", ctypes.c_double)]
+
+
+class TransportResult(ctypes.Structure):
+    """lpg_transport_result."""
+    _fields_ = [("status", ctypes.c_int32), ("started", ctypes.c_int32), ("iterations", ctypes.c_int64),
+                ("objective", ctypes.c_double)]
+
+
+class TransportInfo(ctypes.Structure):
+    """lpg_transport_info_t."""
+    _fields_ = [("count", ctypes.c_int64), ("nr", ctypes.c_int64), ("nc", ctypes.c_int64),
+                ("tier", ctypes.c_int32), ("form", ctypes.c_int32), ("start", ctypes.c_int32), ("chunk", ctypes.c_int32),
+                ("lds_bytes", ctypes.c_int64), ("launches", ctypes.c_int64), ("kernel_ms", ctypes.c_double)]
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -236,6 +254,17 @@ PROTOTYPES = [
     ("lpg_binary_occupancy", ctypes.c_int, [ctypes.c_void_p, c_int64_p]),
     ("lpg_binary_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
     ("lpg_binary_destroy", None, [ctypes.c_void_p]),
+    ("lpg_transport_create", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_uint32]),
+    ("lpg_transport_load", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64,
+                                          c_double_p, c_double_p]),
+    ("lpg_transport_generate", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64]),
+    ("lpg_transport_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(TransportResult)]),
+    ("lpg_transport_get", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, c_double_p, c_double_p,
+                                         c_int64_p]),
+    ("lpg_transport_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TransportInfo)]),
+    ("lpg_transport_last_error", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("lpg_transport_destroy", None, [ctypes.c_void_p]),
 ]
 
 

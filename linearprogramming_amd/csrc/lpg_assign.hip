@@ -50,23 +50,8 @@ struct AssignGeo {
     int32_t state_lds;     // workgroup form with nc > kBlock: 1 the column state is in LDS, 0 in `scratch`
 };
 
-// The bits of x as an unsigned key that orders like x under `<`, -0 and +0
-// equal; a NaN (none occurs: see the cap in lpg.h) lands above +inf.
-__device__ __forceinline__ uint64_t order_key(double x) {
-    uint64_t b = (uint64_t)__double_as_longlong(x);
-    b = (b << 1) ? b : 0ull;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
+// order_key (lpg_device.h): no NaN occurs here, see the cap in lpg.h.
 __device__ __forceinline__ int rdl_int(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-// Lanes of one wave hand values to each other through LDS: the LDS serves a
-// wave's accesses in order, so only the compiler has to be kept from moving
-// them across this point.
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ double sense(double x, int maximize) { return maximize ? -x : x; }
 

@@ -245,6 +245,23 @@ __device__ __forceinline__ int winner_lane(bool mine) {
     return m ? __ffsll((long long)m) - 1 : -1;
 }
 
+// The bits of x as an unsigned key that orders like x under `<`, -0 and +0
+// equal; a NaN lands above +inf (lpg_assign.hip, lpg_transport.hip: keys of
+// values that may be negative).
+__device__ __forceinline__ uint64_t order_key(double x) {
+    uint64_t b = (uint64_t)__double_as_longlong(x);
+    b = (b << 1) ? b : 0ull;
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// Lanes of one wave hand values to each other through LDS: the LDS serves a
+// wave's accesses in order, so only the compiler has to be kept from moving
+// them across this point.
+__device__ __forceinline__ void wave_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // == block_reduce_cand for candidates with theta >= 0 and unique keys
 // (NW waves per block; NW == 1: no LDS, no barrier). LEAD: a barrier first,
 // for callers that may still be reading the previous call's exchange.

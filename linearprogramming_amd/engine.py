@@ -938,3 +938,100 @@ class BinaryBatch:
         x = np.empty((n, self.n), dtype=np.int8)
         self._check(self.lib.lpg_binary_get(self._b, first, n, x.ctypes.data_as(L.c_int8_p)), "lpg_binary_get")
         return x
+
+
+@dataclass
+class TransportResult:
+    status: int
+    iterations: int
+    objective: float
+
+    @property
+    def status_name(self) -> str:
+        return L.STATUS_NAMES.get(self.status, str(self.status))
+
+
+class TransportBatch:
+    """`count` balanced transportation problems of one shape, nr sources by nc
+    sinks, solved on the device by the tableau method (include/lpg.h,
+    "transportation"): a least-cost or northwest-corner start, potentials,
+    pricing and the closed loop. Costs, supplies and demands are integers."""
+
+    STARTS = {"least_cost": L.TRANSPORT_START_LEAST_COST, "northwest": L.TRANSPORT_START_NORTHWEST}
+
+    def __init__(self, count: int, nr: int, nc: int, maximize: bool = False, start: str = "least_cost", device: int = 0,
+                 lib=None):
+        if start not in self.STARTS:
+            raise LPGError(f"TransportBatch: start {start!r}, want 'least_cost' or 'northwest'")
+        self.lib = lib if lib is not None else L.load()
+        self._t = ctypes.c_void_p()
+        flags = (L.TRANSPORT_MAXIMIZE if maximize else 0) | self.STARTS[start]
+        rc = self.lib.lpg_transport_create(ctypes.byref(self._t), device, count, nr, nc, flags)
+        if rc != 0:
+            raise LPGError(f"lpg_transport_create rc={rc}: {self.lib.lpg_transport_last_error(None).decode()}")
+        self.count, self.nr, self.nc, self.maximize, self.start = count, nr, nc, bool(maximize), start
+
+    def close(self):
+        if self._t:
+            self.lib.lpg_transport_destroy(self._t)
+            self._t = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_transport_last_error(self._t).decode()}")
+        return rc
+
+    @property
+    def info(self) -> L.TransportInfo:
+        i = L.TransportInfo()
+        self._check(self.lib.lpg_transport_info(self._t, ctypes.byref(i)), "lpg_transport_info")
+        return i
+
+    def load(self, costs, supply, demand, first: int = 0):
+        """costs [n, nr, nc], supply [n, nr], demand [n, nc]: problems first .. first + n - 1."""
+        c = np.ascontiguousarray(costs, dtype=np.float64)
+        s = np.ascontiguousarray(supply, dtype=np.float64)
+        d = np.ascontiguousarray(demand, dtype=np.float64)
+        n = c.shape[0] if c.ndim == 3 else -1
+        if c.shape != (n, self.nr, self.nc) or s.shape != (n, self.nr) or d.shape != (n, self.nc):
+            raise LPGError(f"load: shapes {c.shape}, {s.shape}, {d.shape}, want [n, {self.nr}, {self.nc}], "
+                           f"[n, {self.nr}], [n, {self.nc}]")
+        self._check(self.lib.lpg_transport_load(self._t, first, n, c.ctypes.data_as(L.c_double_p), self.nc,
+                                                s.ctypes.data_as(L.c_double_p), d.ctypes.data_as(L.c_double_p)),
+                    "lpg_transport_load")
+
+    def generate(self, seed: int = 20220518, range: int = 100, qmax: int = 9):
+        """The generated problems of include/lpg.h ("Generator"), problem q from seed + q."""
+        self._check(self.lib.lpg_transport_generate(self._t, seed, range, qmax), "lpg_transport_generate")
+
+    def solve(self, max_iters: int = None, rule: int = L.RULE_DANTZIG) -> list:
+        """Continues every problem by at most max_iters iterations (default 50 (nr + nc))."""
+        if max_iters is None:
+            max_iters = 50 * (self.nr + self.nc)
+        r = (L.TransportResult * self.count)()
+        self._check(self.lib.lpg_transport_solve(self._t, max_iters, rule, r), "lpg_transport_solve")
+        return [TransportResult(x.status, x.iterations, x.objective) for x in r]
+
+    def get(self, first: int = 0, n: int = None):
+        """(x [n, nr, nc], u [n, nr], v [n, nc], basis [n, nr + nc - 1] int64) of problems first .. first + n - 1."""
+        n = self.count - first if n is None else n
+        x = np.empty((n, self.nr, self.nc), dtype=np.float64)
+        u = np.empty((n, self.nr), dtype=np.float64)
+        v = np.empty((n, self.nc), dtype=np.float64)
+        basis = np.empty((n, self.nr + self.nc - 1), dtype=np.int64)
+        self._check(self.lib.lpg_transport_get(self._t, first, n, x.ctypes.data_as(L.c_double_p),
+                                               u.ctypes.data_as(L.c_double_p), v.ctypes.data_as(L.c_double_p),
+                                               basis.ctypes.data_as(L.c_int64_p)), "lpg_transport_get")
+        return x, u, v, basis

@@ -869,6 +869,86 @@ def solve_assignment(costs, maximize: bool = False, device: int = 0) -> list:
 
 
 @dataclass
+class TransportSolution:
+    """solve_transportation's result for one model, the dummy row or column stripped."""
+    status: str                  # OPTIMAL, ITER_LIMIT, or INFEASIBLE (the optimum ships over a forbidden route)
+    objective: float             # NaN if infeasible
+    x: np.ndarray                # the flows [sources, sinks]
+    u: np.ndarray                # the source potentials
+    v: np.ndarray                # the sink potentials
+    iterations: int
+    unused: np.ndarray           # per source: supply that stays (total supply above total demand), else zeros
+    unmet: np.ndarray            # per sink: demand that is not served (total demand above total supply), else zeros
+
+
+def solve_transportation(models, maximize: bool = False, start: str = "least_cost", rule: int = 0, max_iters: int = None,
+                         device: int = 0) -> list:
+    """The transportation problem of every (costs, supply, demand) of ``models``
+    (include/lpg.h, "transportation"): the models of one shape together in one
+    TransportBatch, the results in input order. Data are integers. An
+    unbalanced model gets a zero-cost dummy column (supply left over) or dummy
+    row (demand not served), which is stripped from the answer and reported as
+    ``unused`` / ``unmet``. A cost of +inf (``maximize``: -inf) forbids a route:
+    it is replaced by a penalty M = (cmax - cmin) T + |cmin| + 1 on the
+    minimised costs, T the total amount, which any plan that ships one unit over
+    such a route pays above every plan that ships none; the model is INFEASIBLE
+    if the optimum still uses one. A penalty outside the library's caps is an
+    error."""
+    from . import _lib as L
+    from .engine import TransportBatch
+    prepared = []
+    for idx, (c, s, d) in enumerate(models):
+        c, s, d = np.asarray(c, dtype=np.float64), np.asarray(s, dtype=np.float64), np.asarray(d, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1 or s.shape != (c.shape[0],) or d.shape != (c.shape[1],):
+            raise FrontendError(f"solve_transportation: model {idx} has shapes {c.shape}, {s.shape}, {d.shape}, want "
+                                f"[nr, nc], [nr], [nc]")
+        if not (np.isfinite(s).all() and np.isfinite(d).all()) or (s < 0).any() or (d < 0).any():
+            raise FrontendError(f"solve_transportation: model {idx} has a supply or demand that is negative or not finite")
+        nr, nc = c.shape
+        cost = -c if maximize else c.copy()                # minimised
+        forbidden = cost == np.inf
+        if np.isnan(cost).any() or (cost == -np.inf).any():
+            raise FrontendError(f"solve_transportation: model {idx} has a NaN cost or an infinity of the wrong sign")
+        diff = s.sum() - d.sum()
+        if diff > 0:                                       # a dummy sink takes what stays
+            cost, forbidden = np.hstack([cost, np.zeros((nr, 1))]), np.hstack([forbidden, np.zeros((nr, 1), dtype=bool)])
+            d = np.append(d, diff)
+        elif diff < 0:                                     # a dummy source serves what is missing
+            cost, forbidden = np.vstack([cost, np.zeros((1, nc))]), np.vstack([forbidden, np.zeros((1, nc), dtype=bool)])
+            s = np.append(s, -diff)
+        if forbidden.any():
+            finite = cost[~forbidden]
+            cmax, cmin = (finite.max(), finite.min()) if finite.size else (0.0, 0.0)
+            total = s.sum()
+            big = (cmax - cmin) * total + abs(cmin) + 1.0
+            if big > L.TRANSPORT_COST_CAP or big * total > 2.0 ** 53:
+                raise FrontendError(f"solve_transportation: model {idx}: the penalty {big:g} of a forbidden route at a "
+                                    f"total amount of {total:g} is outside the caps (2^40, and 2^53 for the product)")
+            cost = np.where(forbidden, big, cost)
+        prepared.append((-cost if maximize else cost, s, d, forbidden, nr, nc, diff))
+    groups = {}
+    for idx, p in enumerate(prepared):
+        groups.setdefault(p[0].shape, []).append(idx)
+    out = [None] * len(prepared)
+    for (gr, gc), members in groups.items():
+        with TransportBatch(len(members), gr, gc, maximize=maximize, start=start, device=device) as t:
+            t.load(np.stack([prepared[i][0] for i in members]), np.stack([prepared[i][1] for i in members]),
+                   np.stack([prepared[i][2] for i in members]))
+            res = t.solve(max_iters, rule)
+            x, u, v, _ = t.get()
+        for q, idx in enumerate(members):
+            _, _, _, forbidden, nr, nc, diff = prepared[idx]
+            r = res[q]
+            status, objective = L.STATUS_NAMES[r.status], float(r.objective)
+            if r.status == L.OPTIMAL and (x[q][forbidden] > 0).any():
+                status, objective = "INFEASIBLE", float("nan")
+            out[idx] = TransportSolution(status, objective, x[q, :nr, :nc].copy(), u[q, :nr].copy(), v[q, :nc].copy(),
+                                         int(r.iterations), x[q, :nr, nc].copy() if diff > 0 else np.zeros(nr),
+                                         x[q, nr, :nc].copy() if diff < 0 else np.zeros(nc))
+    return out
+
+
+@dataclass
 class BinarySolution:
     """solve_binary's result for one 0-1 program, in the caller's column order."""
     status: str                  # OPTIMAL, INFEASIBLE, or ITER_LIMIT (max_nodes reached: the incumbent so far)

@@ -378,7 +378,7 @@ int  lpg_device_sync(lpg_ctx *ctx);
  * host thread; not reentrant. */
 #define LPG_BATCH_TIER_LDS    0
 #define LPG_BATCH_TIER_GLOBAL 1
-#define LPG_BATCH_MAX_DIM     8192   /* m + 1 (Big-M: m + 2) and ncols of a batch */
+#define LPG_BATCH_MAX_DIM     8192   /* m + 1 (Big-M: m + 2, goal: m + K) and ncols of a batch */
 
 typedef struct lpg_batch lpg_batch;
 
@@ -388,7 +388,7 @@ typedef struct {
     int32_t chunk;                /* pivots per LP and launch */
     int64_t lds_bytes;            /* dynamic LDS of one workgroup */
     int64_t log_capacity;         /* pivots recorded per LP (0 with LPG_FLAG_NO_LOG) */
-    int32_t nobj;                 /* objective rows per tableau: 1, or 2 for a Big-M batch */
+    int32_t nobj;                 /* objective rows per tableau: 1, 2 for a Big-M batch, K for a goal batch */
     /* ragged: 1 for a batch from lpg_batch_create_ragged (m, ncols, ld and
      * lds_bytes above are then the largest of any LP, tier is
      * LPG_BATCH_TIER_GLOBAL if any LP is on it), else 0 */
@@ -497,6 +497,66 @@ int  lpg_batch_solve_two_phase(lpg_batch *b, int64_t art_first, const double *co
  * batch from lpg_batch_create: LPG_ERR_STATE. */
 int  lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, int64_t ld_cost,
                            int64_t max_pivots, int rule, lpg_result *out);
+
+/* ---- goal programmes: K priority rows priced on the device ----
+ * Preemptive goal programming: hard constraints, goal rows with deviation
+ * variables d- / d+, and K priority levels P1 >> P2 >> ... >> PK, solved by the
+ * simplex with K rows of check numbers instead of one. A Big-M batch is the
+ * case K = 2 (the M part is level 0) and a plain batch the case K = 1; a goal
+ * batch is nevertheless a kind of its own.
+ *
+ * Layout. A goal batch holds `count` tableaus of (m + K) x ncols,
+ * 1 <= K <= LPG_GOAL_MAX_LEVELS, in max form like every other batch: rows
+ * 0..m-1 the constraints (column 0 the right-hand side) with a basis, row
+ * m + k the objective row of priority level k, level 0 the highest.
+ *
+ * Costs. The caller gives K rows of N = ncols - 1 costs per LP; a minimised
+ * weighted deviation is a negative cost on d- / d+ at its level.
+ *
+ * One call of lpg_batch_solve_goal, per LP, whatever its earlier status:
+ *  1. for k = 0..K-1 row m + k becomes lpo_set_objective(cost_k) from the
+ *     current basis: acc = fma(cost_k[basis[i]-1], T[i][j], acc) over
+ *     i = 0..m-1 in order, then acc - cost_k[j-1] for j >= 1;
+ *  2. the pivot loop is lpg_solve's over columns 1..N, with the pricing class
+ *     of column j found by scanning k = 0, 1, ...: d_k[j] < -eps_opt: the class
+ *     is k and the value d_k[j]; else d_k[j] <= eps_opt: go on to the next
+ *     level; else (positive, or NaN) the column is not eligible. A column with
+ *     no class is not eligible;
+ *  3. the entering column: LPG_RULE_DANTZIG the least class, then the least
+ *     value, then the smallest column; LPG_RULE_BLAND the first eligible column.
+ * The ratio test, the LPG_NUMERIC rule, the update (all K objective rows take
+ * part in it), the log and the order of the checks (price: LPG_OPTIMAL; budget
+ * spent: LPG_ITER_LIMIT; ratio: LPG_UNBOUNDED; LPG_NUMERIC; apply) are
+ * lpg_batch_solve_big_m's, and every call starts from fresh objective rows and
+ * a fresh budget of max_pivots. There is no LPG_INFEASIBLE at this layer: a
+ * caller that puts artificials at level 0 reads attain[q][0].
+ *
+ * Results: lpg_result as elsewhere with objective = T[m + K - 1][0], and
+ * attain[q * K + k] = T[m + k][0] of LP q.
+ *
+ * lpg_batch_load, _get_rows, _get_basis, _get_log, _info (nobj = K),
+ * _set_tolerances, _reserve_log and _destroy serve a goal batch as they serve a
+ * Big-M batch's m + 2 rows. Every other lpg_batch_* call refuses it
+ * (LPG_ERR_STATE, the message names lpg_batch_solve_goal), and
+ * lpg_batch_solve_goal refuses plain and Big-M batches. The tier is decided by
+ * the LDS footprint of m + K rows; there are no ragged goal batches. */
+#define LPG_GOAL_MAX_LEVELS   8
+/* count >= 1 goal programmes of m constraint rows, ncols = N+1 columns and
+ * nlevels priority levels. LPG_ERR_ARG before any device work: nlevels outside
+ * 1..LPG_GOAL_MAX_LEVELS, a bad shape, m + nlevels or ncols over
+ * LPG_BATCH_MAX_DIM, count * (m + nlevels) over 2^31 - 1, flags other than
+ * LPG_FLAG_NO_LOG. */
+int  lpg_batch_create_goal(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, int nlevels,
+                           uint32_t flags);
+/* The call described above. Level k's cost of column j of LP q is
+ * cost[q * ld_lp + k * ld_level + (j - 1)], ld_level >= N and
+ * ld_lp >= nlevels * ld_level; the padding is never read. res[count] and
+ * attain[count x nlevels] may be NULL. NULL cost, a bad rule, ld_level, ld_lp
+ * or max_pivots < 0: LPG_ERR_ARG, the message names the argument and nothing
+ * has pivoted; a batch that is not a goal batch: LPG_ERR_STATE. */
+int  lpg_batch_solve_goal(lpg_batch *b, const double *cost, int64_t ld_lp, int64_t ld_level, int64_t max_pivots,
+                          int rule, lpg_result *res, double *attain /* count x nlevels, or NULL */);
+
 /* lpg_set_objective on every LP: cost = count x N of pitch ld_cost >= N; the
  * objective row of LP i becomes d_j = sum_r c_B(r) T[r][j] - c_j from its
  * current basis, and the LP's status LPG_RUNNING. */

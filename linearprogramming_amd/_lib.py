@@ -27,6 +27,7 @@ FLAG_EAGER = 0x8
 DEFER_MAX = 128
 BATCH_TIER_LDS, BATCH_TIER_GLOBAL = 0, 1
 BATCH_MAX_DIM = 8192
+GOAL_MAX_LEVELS = 8
 BRANCH_MOST_FRACTIONAL, BRANCH_FIRST = 0, 1
 BATCH_MAX_CUTS = 1024
 ASSIGN_MAXIMIZE = 0x1
@@ -205,6 +206,10 @@ PROTOTYPES = [
                                                  ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
     ("lpg_batch_solve_big_m", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, c_double_p, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_int, ctypes.POINTER(Result)]),
+    ("lpg_batch_create_goal", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int, ctypes.c_uint32]),
+    ("lpg_batch_solve_goal", ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int, ctypes.POINTER(Result), c_double_p]),
     ("lpg_batch_set_objective", ctypes.c_int, [ctypes.c_void_p, c_double_p, ctypes.c_int64]),
     ("lpg_batch_generate_artificial", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, c_int64_p]),
     ("lpg_batch_get_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, c_double_p, ctypes.c_int64]),

@@ -28,8 +28,14 @@
 // M part in row m and the real part in row m + 1, and are solved by
 // k_batch_big_m with lexicographic pricing (lpo.c lpo_solve_big_m).
 //
-// The three solve kernels (k_batch_solve, k_batch_two_phase, k_batch_big_m)
-// are their method's state machine over one set of parts: BatchView (where
+// Goal batches (lpg_batch_create_goal) carry K <= LPG_GOAL_MAX_LEVELS objective
+// rows per LP, row m + k the row of priority level k (level 0 the highest),
+// and are solved by k_batch_goal: Big-M's loop with a pricing class per level
+// (batch_price_goal), which at K = 2 is k_batch_big_m's pricing and at K = 1
+// k_batch_solve's.
+//
+// The four solve kernels (k_batch_solve, k_batch_two_phase, k_batch_big_m,
+// k_batch_goal) are their method's state machine over one set of parts: BatchView (where
 // the LP lives, load / store, apply a pivot), batch_primal_step (one step of
 // lpo_solve), batch_objective (an objective row) and batch_write_back.
 //
@@ -143,7 +149,7 @@ struct BatchGeo {
     int32_t  chunk;
     int32_t  pitch;           // TIER_LDS: row pitch in LDS (doubles, odd)
     int32_t  txs;             // update tile: 1 << txs lanes along a row, 256 >> txs rows at a time
-    int32_t  nobj;            // objective rows: 1, or 2 for a Big-M batch (M part in row m, real part in row m + 1)
+    int32_t  nobj;            // objective rows: 1, 2 for a Big-M batch (M part in row m, real part in row m + 1), K of a goal batch
     const BatchShape *shape;  // ragged: one record per LP (then ld, m, ncols, nact, pitch, txs above are not read); else null
     const int32_t *order;     // ragged: workgroup w of this launch owns LP order[w]
 };
@@ -422,6 +428,85 @@ __device__ __forceinline__ int64_t batch_price_big_m(const double *objM, const d
         pp_take(pb, c, pp_better<RULE>(c, pb));
     }
     pb = block_argmin_pp<RULE>(pb);
+    return pb.j;
+}
+
+// block_argmin_pp<RULE_DANTZIG> for partials of more than two classes (its
+// key has one bit for the class): the least class of the wave first, then
+// block_argmin_pp's (value, column) key among the lanes that hold it; the four
+// waves meet in LDS through (class, key). Whole-wave calls only (wave_min_*).
+template <int NW = kBlock / 64>
+__device__ PricePart block_argmin_pp_cls(const PricePart &p) {
+    const bool valid = p.j >= 0;
+    const uint32_t c = valid ? (uint32_t)p.cls : ~0u;
+    const uint32_t cm = wave_min_u32(c);
+    const bool in = valid & (c == cm);
+    uint64_t h = in ? (~(uint64_t)__double_as_longlong(p.v) & 0x7fffffffffffffffull) : ~0ull;
+    uint32_t l = in ? (uint32_t)p.j : ~0u;
+    const uint64_t mh = h;
+    const uint32_t ml = l;
+    wave_min_key(h, l);
+    const int src = winner_lane(in && mh == h && ml == l);
+    PricePart o{0.0, -1, 0, 0};
+    if (src >= 0) {      // wave-uniform
+        o.j = (int64_t)l;
+        o.v = __longlong_as_double((long long)rdl64((uint64_t)__double_as_longlong(p.v), src));
+        o.cls = (int32_t)cm;
+        o.pad = (int32_t)rdl32((uint32_t)p.pad, src);
+    }
+    __shared__ PricePart sw[NW];
+    __shared__ uint64_t sh[NW];
+    __shared__ uint32_t sl[NW], sc[NW];
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        sw[w] = o;
+        sh[w] = h;
+        sl[w] = l;
+        sc[w] = cm;
+    }
+    __syncthreads();
+    int bi = 0;
+    uint32_t bc = sc[0];
+    uint64_t bh = sh[0];
+    uint32_t bl = sl[0];
+#pragma unroll
+    for (int i = 1; i < NW; i++) {
+        const bool t = sc[i] < bc || (sc[i] == bc && key_less(sh[i], sl[i], bh, bl));
+        bc = t ? sc[i] : bc;
+        bh = t ? sh[i] : bh;
+        bl = t ? sl[i] : bl;
+        bi = t ? i : bi;
+    }
+    return sw[bi];
+}
+
+// Goal pricing over columns 1..nact of the nlev objective rows at obj, obj +
+// tp, ... (include/lpg.h, "goal programmes"): the class of a column is the
+// first level k whose d_k < -eps (value d_k), every level before it within
+// [-eps, eps]; a level before it that is positive or NaN makes the column
+// ineligible. The levels are walked from the last to the first (a scalar
+// loop: nlev is uniform), level k overwriting what the later levels left, by
+// selects on its two predicates: no branch diverges per lane.
+template <int RULE>
+__device__ __forceinline__ int64_t batch_price_goal(const double *obj, int64_t tp, int nlev, int64_t nact, double eps_opt,
+                                                    int tid) {
+    PricePart pb{0.0, -1, 0, 0};
+    for (int64_t j = 1 + tid; j <= nact; j += kBlock) {
+        double val = 0.0;
+        int32_t cls = 0;
+        bool ok = false;
+        for (int k = nlev - 1; k >= 0; k--) {
+            const double d = obj[k * tp + j];
+            const bool neg = d < -eps_opt, blocks = !(d <= eps_opt);
+            val = neg ? d : val;
+            cls = neg ? k : cls;
+            ok = neg | (ok & !blocks);
+        }
+        PricePart c{val, ok ? j : -1, cls, (int32_t)j};
+        pp_take(pb, c, pp_better<RULE>(c, pb));
+    }
+    pb = RULE == RULE_BLAND ? block_argmin_pp<RULE_BLAND>(pb) : block_argmin_pp_cls(pb);
     return pb.j;
 }
 
@@ -750,6 +835,60 @@ __global__ __launch_bounds__(kBlock) void k_batch_big_m(BatchGeo g, TwoPhase t) 
     if (v.tid == 0) {
         batch_write_back(g, v, lp, status, pst, pivots, last_k, last_r, budget);
         lp->phase = phase;
+    }
+}
+
+// ------------------------------------------------------------------------
+// preemptive goal programme of one LP (include/lpg.h, "goal programmes"):
+// tableaus of m + K rows, row m + k the objective row of priority level k
+// ------------------------------------------------------------------------
+
+struct GoalArgs {
+    const double *cost;       // count x K x N: level k of LP q at (q * K + k) * N
+    double *attain;           // count x K: column 0 of the objective rows after the launch
+};
+
+// k_batch_big_m's state machine with K = g.nobj rows: PH_OBJ1 = the K
+// objective rows are still to be set (one unit of work), PH_LOOP1 = in the
+// pivot loop, so a launch that ends in front of any unit is resumed bitwise.
+template <int RULE, int TIER>
+__global__ __launch_bounds__(kBlock) void k_batch_goal(BatchGeo g, GoalArgs a) {
+    const int64_t lpi = blockIdx.x;
+    BatchLP *lp = g.lp + lpi;
+    if (lp->status != RUNNING) return;            // finished in an earlier launch of this call: uniform
+    const int nlev = g.nobj;
+    const LpGeo s = lp_geo<false>(g, lpi, nlev, 0);
+    const BatchView<TIER> v = BatchView<TIER>::make(g, s, s.m + nlev);
+    const int64_t m = s.m, N = s.ncols - 1, chunk = g.chunk;
+    const double *cost = a.cost + lpi * nlev * N;
+    int32_t phase = lp->phase, pst = lp->pstatus;
+    int64_t pivots = lp->pivots, budget = lp->budget, last_k = lp->last_k, last_r = lp->last_r;
+    v.load();
+
+    int64_t work = 0;
+    if (phase == PH_OBJ1) {
+        // lpo_set_objective with level k's costs into row m + k, each from the current basis (rows 0..m-1 only)
+        for (int k = 0; k < nlev; k++) batch_objective<COST_REAL>(v, m + k, cost + k * N, 0);
+        pst = RUNNING;                            // lpo_set_objective
+        phase = PH_LOOP1;
+        work = 1;
+    }
+    // lpo_solve over columns 1..N, priced on the K rows
+    auto price = [&] { return batch_price_goal<RULE>(v.T + m * v.tp, v.tp, nlev, N, g.eps_opt, v.tid); };
+    int32_t status;                               // RUNNING where the launch ends in front of a unit
+    while ((status = batch_primal_step<RULE>(v, price, g.eps_piv, budget, chunk - work, pivots, last_k, last_r)) ==
+           STEP_APPLIED) {
+        pivots++;
+        budget--;
+        work++;
+    }
+    if (status != RUNNING && status != ITER_LIMIT) pst = status;   // lpo_ctx.status
+
+    v.store(work > 0);
+    if (v.tid == 0) {
+        batch_write_back(g, v, lp, status, pst, pivots, last_k, last_r, budget);
+        lp->phase = phase;
+        for (int k = 0; k < nlev; k++) a.attain[lpi * nlev + k] = v.T[(m + k) * v.tp];
     }
 }
 
@@ -1289,6 +1428,7 @@ struct lpg_batch {
     int device = 0;
     int64_t count = 0, m = 0, ncols = 0, ld = 0, nact = 0;
     int nobj = 1;                 // 2: a Big-M batch (lpg_batch_create_big_m), tableaus of m + 2 rows
+    bool goal = false;            // a goal batch (lpg_batch_create_goal): nobj = K priority levels, tableaus of m + K rows
     uint32_t flags = 0;
     double eps_piv = 1e-9, eps_opt = 1e-9;
     int tier = TIER_LDS;
@@ -1304,6 +1444,7 @@ struct lpg_batch {
     int32_t *running = nullptr;
     unsigned long long *bad = nullptr;
     double *cost = nullptr;       // count x N real costs of two-phase and Big-M calls / set_objective (allocated on first use)
+    double *attain = nullptr;     // goal batch: count x K attained levels (its cost is count x K x N; both allocated on first use)
     hipStream_t stream = nullptr;
     char err[512] = {0};
     // A round of a solve call is one launch per group: LPs order[first .. first + count)
@@ -1417,7 +1558,7 @@ int alloc_log(lpg_batch *b, int64_t cap) {
 }
 
 // which solver a call runs
-enum Method { M_PRIMAL, M_DUAL, M_TWO_PHASE, M_BIG_M };
+enum Method { M_PRIMAL, M_DUAL, M_TWO_PHASE, M_BIG_M, M_GOAL };
 
 // the dynamic LDS limit of kernel K (`name` for the error message) raised to `bytes`, once per device
 template <auto K>
@@ -1460,7 +1601,17 @@ int launch_tier(lpg_batch *b, const lpg_batch::Group &gr, Method method, int rul
     }
 }
 
+template <int TIER>
+int launch_goal(lpg_batch *b, const lpg_batch::Group &gr, int rule, const GoalArgs &a) {
+    return rule == RULE_BLAND ? launch_lp<k_batch_goal<RULE_BLAND, TIER>>(b, gr, "k_batch_goal", a)
+                              : launch_lp<k_batch_goal<RULE_DANTZIG, TIER>>(b, gr, "k_batch_goal", a);
+}
+
 int launch_solve(lpg_batch *b, const lpg_batch::Group &gr, Method method, int rule, const TwoPhase &t) {
+    if (method == M_GOAL) {
+        const GoalArgs a{b->cost, b->attain};
+        return gr.tier == TIER_LDS ? launch_goal<TIER_LDS>(b, gr, rule, a) : launch_goal<TIER_GLOBAL>(b, gr, rule, a);
+    }
     if (b->ragged)
         return gr.tier == TIER_LDS ? launch_tier<TIER_LDS, true>(b, gr, method, rule, t)
                                    : launch_tier<TIER_GLOBAL, true>(b, gr, method, rule, t);
@@ -1478,8 +1629,15 @@ int wrong_layout(lpg_batch *b, const char *call, const char *other) {
                                    "nothing has moved or pivoted", call, other);
 }
 
-// what a Big-M batch refuses (and a plain batch, for lpg_batch_solve_big_m)
+// a plain batch: neither Big-M nor goal
+bool plain(const lpg_batch *b) { return b->nobj == 1 && !b->goal; }
+
+// what a Big-M batch and a goal batch refuse (and a plain batch, for lpg_batch_solve_big_m)
 int wrong_kind(lpg_batch *b, const char *call) {
+    if (b->goal)
+        return bfail(b, LPG_ERR_STATE, "%s: this is a goal batch (lpg_batch_create_goal, %d objective rows); only "
+                                       "lpg_batch_solve_goal pivots it, and lpg_batch_load, _get_rows, _get_basis, _get_log, "
+                                       "_info and _set_tolerances serve it; nothing has moved or pivoted", call, b->nobj);
     if (b->nobj == 2)
         return bfail(b, LPG_ERR_STATE, "%s: this is a Big-M batch (lpg_batch_create_big_m, two objective rows); only "
                                        "lpg_batch_solve_big_m pivots it; nothing has pivoted", call);
@@ -1529,10 +1687,10 @@ int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_res
         // both phases have a budget of up to max_pivots, and the drive-out
         // pivots (at most m) and the two objectives are work as well
         max_launches = 2 * std::min<int64_t>(max_pivots / b->chunk, (int64_t)1 << 60) + (b->m + 2) / b->chunk + 4;
-    } else if (method == M_BIG_M) {
+    } else if (method == M_BIG_M || method == M_GOAL) {
         max_launches = max_pivots / b->chunk + 4;                 // the pivots and one objective unit
     }
-    if (method == M_TWO_PHASE || method == M_BIG_M)
+    if (method == M_TWO_PHASE || method == M_BIG_M || method == M_GOAL)
         hipLaunchKernelGGL(k_batch_begin_two_phase, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp,
                            b->count, max_pivots);
     else
@@ -1587,7 +1745,7 @@ int push_shapes(lpg_batch *b) {
 int solve_artificial(lpg_batch *b, Method method, const char *call, bool packed, const int64_t *art_first,
                      const double *cost, int64_t ld_cost, int64_t max_pivots, int rule, lpg_result *out) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
-    if ((b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
+    if (b->goal || (b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
     if (b->ragged != packed) {
         if (packed) return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m" : "lpg_batch_solve_two_phase");
         return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m_ragged" : "lpg_batch_solve_two_phase_ragged");
@@ -1729,9 +1887,10 @@ int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector
     return 0;
 }
 
-// lpg_batch_create (nobj = 1) and lpg_batch_create_big_m (nobj = 2); `call` names the entry point
+// lpg_batch_create (nobj = 1), lpg_batch_create_big_m (nobj = 2) and lpg_batch_create_goal (`goal`, nobj = K);
+// `call` names the entry point
 int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags, int nobj,
-                 const char *call) {
+                 const char *call, bool goal = false) {
     if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (count < 1 || m < 1 || ncols < 2)
@@ -1759,6 +1918,7 @@ int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t 
     b->ld = ld;
     b->nact = ncols - 1;
     b->nobj = nobj;
+    b->goal = goal;
     b->flags = flags;
     const bool force_global = env_is("LPG_BATCH_TIER", "global");
     b->tier = (!force_global && lds_bytes(TIER_LDS, m, ncols, nobj) <= kBatchMaxLds) ? TIER_LDS : TIER_GLOBAL;
@@ -2030,7 +2190,7 @@ int lpg_batch_scenario(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *
     if (!src || !ident || !rhs)
         return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !ident ? "ident" : "rhs");
     if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
-    if (p->nobj == 2) return wrong_kind(p, call);
+    if (!plain(p)) return wrong_kind(p, call);
     for (int64_t c = 0; c < n; c++)
         if (int rc = src_ok(p, call, c, src[c])) return rc;
     if (int rc = ident_ok(p, call, ident)) return rc;
@@ -2066,7 +2226,7 @@ int lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs) {
     const char *call = "lpg_batch_set_rhs";
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
     if (!ident || !rhs) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !ident ? "ident" : "rhs");
-    if (b->nobj == 2) return wrong_kind(b, call);
+    if (!plain(b)) return wrong_kind(b, call);
     if (int rc = ident_ok(b, call, ident)) return rc;
     for (int64_t q = 0, at = 0; q < b->count; at += lp_m(b, q), q++)
         if (int rc = rhs_ok(b, call, rhs, at, lp_m(b, q), "LP", q)) return rc;
@@ -2104,7 +2264,7 @@ int lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *o
         return bfail(b, LPG_ERR_ARG, "%s: out: %d of rhs_lo, rhs_hi, rhs_lo_at, rhs_hi_at given (all four or none)", call, nrhs);
     if (!out->dual && !ncost && !nrhs)
         return bfail(b, LPG_ERR_ARG, "%s: out: none of dual, cost_*, rhs_* given (nothing to compute)", call);
-    if (b->nobj == 2) return wrong_kind(b, call);
+    if (!plain(b)) return wrong_kind(b, call);
     if (int rc = ident_ok(b, call, ident)) return rc;
     BHIPCHK(b, hipSetDevice(b->device));
     if (int rc = b->ragged ? raise_lds<k_batch_ranging<true>>(b, "k_batch_ranging", kRangingMaxLds)
@@ -2154,7 +2314,7 @@ int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, in
     const char *call = "lpg_batch_branch_select";
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
     if (!mask || !out) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
-    if (b->nobj == 2) return wrong_kind(b, call);
+    if (!plain(b)) return wrong_kind(b, call);
     if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
     if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
     if (rule != LPG_BRANCH_MOST_FRACTIONAL && rule != LPG_BRANCH_FIRST) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
@@ -2193,7 +2353,7 @@ int lpg_batch_branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *sr
             return bfail(p, LPG_ERR_ARG, "%s: dir[%lld] = %d (-1: x <= floor(v), +1: x >= ceil(v))", call, (long long)c,
                          (int)dir[c]);
     if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
-    if (p->nobj == 2) return wrong_kind(p, call);
+    if (!plain(p)) return wrong_kind(p, call);
     for (int64_t c = 0; c < n; c++) {
         if (int rc = src_ok(p, call, c, src[c])) return rc;
         const int64_t m = lp_m(p, src[c]), ncols = lp_ncols(p, src[c]);
@@ -2227,7 +2387,7 @@ int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64
         return bfail(b, LPG_ERR_ARG, "%s: max_cuts = %lld outside 1..%d", call, (long long)max_cuts, LPG_BATCH_MAX_CUTS);
     if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
-    if (b->nobj == 2) return wrong_kind(b, call);
+    if (!plain(b)) return wrong_kind(b, call);
     if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
     BHIPCHK(b, hipSetDevice(b->device));
     const size_t nbytes = (size_t)b->count * sizeof(int64_t), rbytes = nbytes * (size_t)max_cuts;
@@ -2266,7 +2426,7 @@ int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, 
                                          "one cut)", call, (long long)(c + 1), (long long)first[c + 1], (long long)c,
                          (long long)first[c]);
     if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
-    if (p->nobj == 2) return wrong_kind(p, call);
+    if (!plain(p)) return wrong_kind(p, call);
     if (int rc = mask_ok(p, call, nmask, ld_mask)) return rc;
     std::vector<int64_t> ks((size_t)n);
     std::vector<char> seen;
@@ -2325,6 +2485,62 @@ int lpg_batch_create_big_m(lpg_batch **out, int device, int64_t count, int64_t m
     return batch_create(out, device, count, m, ncols, flags, 2, "lpg_batch_create_big_m");
 }
 
+int lpg_batch_create_goal(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, int nlevels, uint32_t flags) {
+    if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (nlevels < 1 || nlevels > LPG_GOAL_MAX_LEVELS)
+        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create_goal: nlevels = %d outside 1..%d (LPG_GOAL_MAX_LEVELS)", nlevels,
+                     LPG_GOAL_MAX_LEVELS);
+    return batch_create(out, device, count, m, ncols, flags, nlevels, "lpg_batch_create_goal", true);
+}
+
+int lpg_batch_solve_goal(lpg_batch *b, const double *cost, int64_t ld_lp, int64_t ld_level, int64_t max_pivots, int rule,
+                         lpg_result *res, double *attain) {
+    const char *call = "lpg_batch_solve_goal";
+    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (!b->goal) {
+        if (b->nobj == 2) return wrong_kind(b, call);
+        return bfail(b, LPG_ERR_STATE, "%s: the batch has one objective row (lpg_batch_create); a goal programme needs a "
+                                       "batch from lpg_batch_create_goal; nothing has pivoted", call);
+    }
+    const int64_t N = b->ncols - 1, K = b->nobj;
+    if (!cost) return bfail(b, LPG_ERR_ARG, "%s: cost is NULL (a goal batch keeps no costs of its own)", call);
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    if (ld_level < N) return bfail(b, LPG_ERR_ARG, "%s: ld_level %lld < N = %lld", call, (long long)ld_level, (long long)N);
+    if (ld_lp / K < ld_level)
+        return bfail(b, LPG_ERR_ARG, "%s: ld_lp %lld < nlevels * ld_level = %lld x %lld", call, (long long)ld_lp, (long long)K,
+                     (long long)ld_level);
+    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
+    BHIPCHK(b, hipSetDevice(b->device));
+    // the costs packed (the caller's padding is never read), and the attained levels beside them
+    const size_t total = (size_t)b->count * (size_t)K * (size_t)N;
+    if (!b->cost && hipMalloc(&b->cost, total * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        b->cost = nullptr;
+        return bfail(b, LPG_ERR_OOM, "hipMalloc(%d levels of costs of %lld LPs) failed", b->nobj, (long long)b->count);
+    }
+    if (!b->attain && hipMalloc(&b->attain, (size_t)b->count * (size_t)K * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        b->attain = nullptr;
+        return bfail(b, LPG_ERR_OOM, "hipMalloc(%d attained levels of %lld LPs) failed", b->nobj, (long long)b->count);
+    }
+    if (ld_level == N && ld_lp == K * N) {                        // no padding: the caller's array is the packed one
+        BHIPCHK(b, hipMemcpy(b->cost, cost, total * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+        double *packed = (double *)malloc(total * sizeof(double));
+        if (!packed) return bfail(b, LPG_ERR_OOM, "%s: malloc(%zu bytes to pack the costs) failed", call, total * sizeof(double));
+        for (int64_t q = 0; q < b->count; q++)
+            for (int64_t k = 0; k < K; k++)
+                memcpy(packed + (size_t)((q * K + k) * N), cost + q * ld_lp + k * ld_level, (size_t)N * sizeof(double));
+        const hipError_t e = hipMemcpy(b->cost, packed, total * sizeof(double), hipMemcpyHostToDevice);
+        free(packed);
+        BHIPCHK(b, e);
+    }
+    if (int rc = batch_run(b, max_pivots, M_GOAL, rule, res)) return rc;
+    if (attain) BHIPCHK(b, hipMemcpy(attain, b->attain, (size_t)b->count * (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 void lpg_batch_destroy(lpg_batch *b) {
     if (!b) return;
     if (b->T || b->stream) (void)hipSetDevice(b->device);
@@ -2340,6 +2556,7 @@ void lpg_batch_destroy(lpg_batch *b) {
     if (b->running) (void)hipFree(b->running);
     if (b->bad) (void)hipFree(b->bad);
     if (b->cost) (void)hipFree(b->cost);
+    if (b->attain) (void)hipFree(b->attain);
     if (b->dshape) (void)hipFree(b->dshape);
     if (b->dorder) (void)hipFree(b->dorder);
     delete b;
@@ -2377,6 +2594,7 @@ int lpg_batch_shape(const lpg_batch *cb, int64_t lp, lpg_batch_shape_t *o) {
 
 int lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, const int64_t *basis) {
     if (!b || !tableaus) return bfail(b, LPG_ERR_ARG, "lpg_batch_load_packed: NULL argument");
+    if (b->goal) return wrong_kind(b, "lpg_batch_load_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_load_packed", "lpg_batch_load");
     if (int rc = range_ok(b, "lpg_batch_load_packed", first, n)) return rc;
     if (n == 0) return 0;
@@ -2415,6 +2633,7 @@ int lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *
 
 int lpg_batch_get_rows_packed(lpg_batch *b, int64_t first, int64_t n, double *out) {
     if (!b || !out) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows_packed: NULL argument");
+    if (b->goal) return wrong_kind(b, "lpg_batch_get_rows_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_get_rows_packed", "lpg_batch_get_rows");
     if (int rc = range_ok(b, "lpg_batch_get_rows_packed", first, n)) return rc;
     if (n == 0) return 0;
@@ -2433,6 +2652,7 @@ int lpg_batch_get_rows_packed(lpg_batch *b, int64_t first, int64_t n, double *ou
 
 int lpg_batch_get_basis_packed(lpg_batch *b, int64_t first, int64_t n, int64_t *basis) {
     if (!b || !basis) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_basis_packed: NULL argument");
+    if (b->goal) return wrong_kind(b, "lpg_batch_get_basis_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_get_basis_packed", "lpg_batch_get_basis");
     if (int rc = range_ok(b, "lpg_batch_get_basis_packed", first, n)) return rc;
     if (n == 0) return 0;
@@ -2445,7 +2665,7 @@ int lpg_batch_get_basis_packed(lpg_batch *b, int64_t first, int64_t n, int64_t *
 
 int lpg_batch_set_objective_packed(lpg_batch *b, const double *cost) {
     if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective_packed: NULL argument");
-    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_set_objective_packed");
+    if (!plain(b)) return wrong_kind(b, "lpg_batch_set_objective_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_set_objective_packed", "lpg_batch_set_objective");
     BHIPCHK(b, hipSetDevice(b->device));
     if (int rc = stage_costs(b, cost, 0)) return rc;
@@ -2494,7 +2714,7 @@ int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableau
 
 int lpg_batch_generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
-    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_generate");
+    if (!plain(b)) return wrong_kind(b, "lpg_batch_generate");
     if (b->ragged) return wrong_layout(b, "lpg_batch_generate", "lpg_batch_load_packed (a ragged batch has no generator)");
     if (n < 1 || b->ncols != n + b->m + 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
@@ -2512,7 +2732,7 @@ int lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt) {
 }
 
 int lpg_batch_set_active_columns(lpg_batch *b, int64_t nact) {
-    if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_set_active_columns");
+    if (b && !plain(b)) return wrong_kind(b, "lpg_batch_set_active_columns");
     if (b && b->ragged)
         return wrong_layout(b, "lpg_batch_set_active_columns", "lpg_batch_solve_two_phase_ragged, which sets them per LP");
     if (!b || nact < 1 || nact > b->ncols - 1)
@@ -2532,13 +2752,13 @@ int lpg_batch_reserve_log(lpg_batch *b, int64_t npivots) {
 }
 
 int lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out) {
-    if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_solve");
+    if (b && !plain(b)) return wrong_kind(b, "lpg_batch_solve");
     if (b && rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve: rule %d", rule);
     return batch_run(b, max_pivots, M_PRIMAL, rule, out);
 }
 
 int lpg_batch_solve_dual(lpg_batch *b, int64_t max_pivots, lpg_result *out) {
-    if (b && b->nobj == 2) return wrong_kind(b, "lpg_batch_solve_dual");
+    if (b && !plain(b)) return wrong_kind(b, "lpg_batch_solve_dual");
     return batch_run(b, max_pivots, M_DUAL, RULE_DANTZIG, out);
 }
 
@@ -2554,7 +2774,7 @@ int lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, i
 
 int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
     if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: NULL argument");
-    if (b->nobj == 2) return wrong_kind(b, "lpg_batch_set_objective");
+    if (!plain(b)) return wrong_kind(b, "lpg_batch_set_objective");
     if (b->ragged) return wrong_layout(b, "lpg_batch_set_objective", "lpg_batch_set_objective_packed");
     if (ld_cost < b->ncols - 1)
         return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: ld_cost %lld < N = %lld", (long long)ld_cost,
@@ -2569,6 +2789,7 @@ int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
 
 int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_t *art_first) {
     if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (b->goal) return wrong_kind(b, "lpg_batch_generate_artificial");
     if (b->ragged)
         return wrong_layout(b, "lpg_batch_generate_artificial", "lpg_batch_load_packed (a ragged batch has no generator)");
     if (n < 1 || b->ncols != n + b->m + 1)

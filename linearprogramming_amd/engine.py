@@ -315,7 +315,9 @@ class BatchEngine:
     """`count` LPs of one shape, each an (m+1) x ncols tableau, solved in one
     launch with one workgroup per LP (include/lpg.h, "batches"). ``big_m=True``:
     a Big-M batch, (m+2) x ncols tableaus (row m the M part, row m + 1 the real
-    part of the objective), solved by solve_big_m only.
+    part of the objective), solved by solve_big_m only. ``levels=K``: a goal
+    batch, (m+K) x ncols tableaus (row m + k the objective row of priority level
+    k, level 0 the highest), solved by solve_goal only.
 
     ``BatchEngine.ragged(shapes)`` makes a ragged batch instead: LP q has its own
     (m, ncols) = shapes[q], and the solve calls still run all of them in one
@@ -328,16 +330,24 @@ class BatchEngine:
         return RaggedBatchEngine(shapes, device=device, big_m=big_m, flags=flags, lib=lib)
 
     def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None, big_m: bool = False,
-                 _handle=None):
+                 _handle=None, levels: int = None):
         """``_handle``: an lpg_batch of this shape that the library already made (branch()); the engine owns it."""
         self.lib = lib if lib is not None else L.load()
         self._b = ctypes.c_void_p() if _handle is None else _handle
+        if levels is not None and big_m:
+            raise LPGError("BatchEngine: big_m and levels exclude each other (a goal batch of 2 levels is no Big-M batch)")
         if _handle is None:
-            name = "lpg_batch_create_big_m" if big_m else "lpg_batch_create"
-            rc = getattr(self.lib, name)(ctypes.byref(self._b), device, count, m, ncols, flags)
+            if levels is not None:
+                name = "lpg_batch_create_goal"
+                rc = self.lib.lpg_batch_create_goal(ctypes.byref(self._b), device, count, m, ncols, levels, flags)
+            else:
+                name = "lpg_batch_create_big_m" if big_m else "lpg_batch_create"
+                rc = getattr(self.lib, name)(ctypes.byref(self._b), device, count, m, ncols, flags)
             if rc != 0:
                 raise LPGError(f"{name} rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
-        self.count, self.m, self.ncols, self.nobj = count, m, ncols, 2 if big_m else 1
+        self.count, self.m, self.ncols = count, m, ncols
+        self.nobj = levels if levels is not None else (2 if big_m else 1)
+        self.levels = levels
 
     def close(self):
         if self._b:
@@ -436,6 +446,25 @@ class BatchEngine:
                     "lpg_batch_solve_big_m")
         del keep
         return [_res(x) for x in r]
+
+    def solve_goal(self, costs, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG):
+        """The preemptive goal programme of every LP of a goal batch in one launch (include/lpg.h, "goal
+        programmes"). costs: [count, K, >= N] (or [K, >= N], the same for every LP), row k the costs of priority
+        level k. Returns (results, attain[count, K]): attain[q, k] is column 0 of LP q's objective row of level k.
+        Every call sets the K objective rows anew from the current basis and has a budget of its own."""
+        K = self.nobj
+        c = np.asarray(costs, dtype=np.float64)
+        if c.ndim == 2:
+            c = np.tile(c, (self.count, 1, 1))
+        c = np.ascontiguousarray(c)
+        if c.ndim != 3 or c.shape[0] != self.count or c.shape[1] != K:
+            raise LPGError(f"solve_goal: costs of shape {c.shape}, want [{self.count}, {K}, >= {self.ncols - 1}]")
+        r = (L.Result * self.count)()
+        attain = np.zeros((self.count, K), dtype=np.float64)
+        self._check(self.lib.lpg_batch_solve_goal(self._b, c.ctypes.data_as(L.c_double_p), K * c.shape[2], c.shape[2],
+                                                  max_pivots, rule, r, attain.ctypes.data_as(L.c_double_p)),
+                    "lpg_batch_solve_goal")
+        return [_res(x) for x in r], attain
 
     def set_objective(self, cost):
         """Engine.set_objective on every LP; cost: [N] or [count, >= N]."""

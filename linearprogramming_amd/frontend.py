@@ -816,6 +816,152 @@ def solve_batch(sms, rule=None, device: int = 0, *, method: str = "two_phase", r
 
 
 @dataclass
+class GoalModel:
+    """A preemptive goal programme over n variables x >= 0 (include/lpg.h, "goal programmes").
+    Hard rows: A x (sense) b with sense -1 (<=), 0 (=) or +1 (>=). Goal rows: G x + d- - d+ = target with
+    d-, d+ >= 0. ``under[i]`` / ``over[i]``: None, or (level, weight > 0): the weight of goal i's
+    under-achievement d- / over-achievement d+ in the sum that priority level ``level`` (1 the highest)
+    minimises."""
+    A: object
+    sense: object
+    b: object
+    G: object
+    target: object
+    under: list
+    over: list
+
+
+@dataclass
+class GoalSolution:
+    """solve_goal's result for one model."""
+    status: str                  # OPTIMAL / UNBOUNDED / INFEASIBLE / ITER_LIMIT / NUMERIC
+    x: np.ndarray                # [n]; NaN unless OPTIMAL, like under, over and attained
+    under: np.ndarray            # d- of every goal
+    over: np.ndarray             # d+ of every goal
+    attained: np.ndarray         # [L]: the weighted deviation that user level 1..L ends with
+    pivots: int
+
+
+def goal_arrays(model: GoalModel, idx: int = 0):
+    """What solve_goal hands to a goal batch for ``model``: (rows [m, ncols] float64, basis [m] int64,
+    costs [K, ncols - 1] float64, nart, L). Rows: the hard rows, then the goal rows; a row with a negative
+    right-hand side is multiplied by -1 (a hard row's sense turns, a goal row's d- and d+ swap signs).
+    Columns: [b | x_1..x_n | d-_1 d+_1 .. d-_g d+_g | a slack (<=) or surplus (>=) per hard row that has
+    one, in row order | an artificial per hard = or >= row, in row order]. Basis: the slack, the
+    artificial, or the deviation column that holds +1. With artificials K = L + 1 and device level 0 is
+    theirs (cost -1 each), user level l being device level l; without, K = L and user level l is device
+    level l - 1. A minimised deviation is the negative cost -weight at its level."""
+    from . import _lib as L_
+    A, G = np.atleast_2d(np.asarray(model.A, dtype=np.float64)), np.atleast_2d(np.asarray(model.G, dtype=np.float64))
+    b, t = np.asarray(model.b, dtype=np.float64).reshape(-1), np.asarray(model.target, dtype=np.float64).reshape(-1)
+    sense = np.asarray(model.sense, dtype=np.int64).reshape(-1)
+    nh, ng = b.shape[0], t.shape[0]
+    if A.size == 0:
+        A = np.zeros((0, G.shape[1]))
+    n = G.shape[1]
+    if ng < 1 or n < 1 or A.shape != (nh, n) or G.shape != (ng, n) or sense.shape != (nh,):
+        raise FrontendError(f"solve_goal: model {idx} has shapes A {A.shape}, sense {sense.shape}, b {b.shape}, G {G.shape}, "
+                            f"target {t.shape}; want [h, n], [h], [h], [g, n], [g] with g >= 1")
+    if not all(np.isfinite(a).all() for a in (A, b, G, t)) or not np.isin(sense, (-1, 0, 1)).all():
+        raise FrontendError(f"solve_goal: model {idx} has an entry that is not finite, or a sense other than -1, 0, +1")
+    if len(model.under) != ng or len(model.over) != ng:
+        raise FrontendError(f"solve_goal: model {idx} has {ng} goals but {len(model.under)} / {len(model.over)} priorities")
+    top = 0
+    for pr in list(model.under) + list(model.over):
+        if pr is None:
+            continue
+        level, weight = pr
+        if int(level) != level or level < 1 or not (weight > 0) or not np.isfinite(weight):
+            raise FrontendError(f"solve_goal: model {idx} has the priority {pr!r}; want (level >= 1, weight > 0)")
+        top = max(top, int(level))
+    if top < 1:
+        raise FrontendError(f"solve_goal: model {idx} minimises no deviation")
+    if top + 1 > L_.GOAL_MAX_LEVELS:
+        raise FrontendError(f"solve_goal: model {idx} has {top} priority levels; with the level of the artificials "
+                            f"that is more than the {L_.GOAL_MAX_LEVELS} a goal batch prices")
+    flip = b < 0
+    A, b, sense = np.where(flip[:, None], -A, A), np.where(flip, -b, b), np.where(flip, -sense, sense)
+    nslack, nart = int((sense != 0).sum()), int((sense >= 0).sum())
+    m, ncols = nh + ng, 1 + n + 2 * ng + nslack + nart
+    K, shift = (top + 1, 0) if nart else (top, 1)
+    rows, basis, costs = np.zeros((m, ncols)), np.zeros(m, dtype=np.int64), np.zeros((K, ncols - 1))
+    s, a = 1 + n + 2 * ng, 1 + n + 2 * ng + nslack
+    for i in range(nh):
+        rows[i, 0], rows[i, 1:1 + n] = b[i], A[i]
+        if sense[i] != 0:
+            rows[i, s] = -float(sense[i])
+            if sense[i] < 0:
+                basis[i] = s
+            s += 1
+        if sense[i] >= 0:
+            rows[i, a], basis[i], costs[0, a - 1] = 1.0, a, -1.0
+            a += 1
+    for i in range(ng):
+        r, dm, dp = nh + i, 1 + n + 2 * i, 2 + n + 2 * i
+        sign = -1.0 if t[i] < 0 else 1.0
+        rows[r, 0], rows[r, 1:1 + n] = sign * t[i], sign * G[i]
+        rows[r, dm], rows[r, dp] = sign, -sign
+        basis[r] = dm if sign > 0 else dp
+        for col, pr in ((dm, model.under[i]), (dp, model.over[i])):
+            if pr is not None:
+                costs[int(pr[0]) - shift, col - 1] = -float(pr[1])
+    return rows, basis, costs, nart, top
+
+
+def solve_goal(models, rule=None, device: int = 0, max_pivots: int = None) -> list:
+    """The preemptive goal programme of every GoalModel of ``models``: the models of one (m, ncols, K)
+    together in one goal batch (goal_arrays says what is loaded), one launch per group, the results in
+    input order. A model whose hard rows need artificials is INFEASIBLE where their level ends below
+    -1e-9 max(1, sum_i |T[i][0]|), Big-M's test. ``max_pivots``: 50 (m + ncols) by default."""
+    from . import _lib as L
+    from .engine import BatchEngine
+    if rule is None:
+        rule = L.RULE_DANTZIG
+    arrays = [goal_arrays(mod, idx) for idx, mod in enumerate(models)]
+    groups = {}
+    for idx, (rows, _, costs, _, _) in enumerate(arrays):
+        groups.setdefault((rows.shape[0], rows.shape[1], costs.shape[0]), []).append(idx)
+    out = [None] * len(arrays)
+    for (m, ncols, K), members in groups.items():
+        T = np.zeros((len(members), m + K, ncols))
+        for q, idx in enumerate(members):
+            T[q, :m] = arrays[idx][0]
+        with BatchEngine(len(members), m, ncols, device=device, levels=K) as e:
+            e.load(T, np.array([arrays[idx][1] for idx in members], dtype=np.int64))
+            res, attain = e.solve_goal(np.array([arrays[idx][2] for idx in members]),
+                                       50 * (m + ncols) if max_pivots is None else max_pivots, rule)
+            rows, bas = e.get_rows(), e.get_basis()
+        for q, idx in enumerate(members):
+            out[idx] = _goal_readout(models[idx], arrays[idx], res[q].status, int(res[q].pivots), attain[q], rows[q, :m, 0],
+                                     bas[q])
+    return out
+
+
+def _goal_readout(model, arrays, status, pivots, attain, xb, bas) -> GoalSolution:
+    """GoalSolution of one model from its status, attained device levels, x_B and basis."""
+    from . import _lib as L
+    _, _, costs, nart, top = arrays
+    ng = len(model.under)
+    n = np.atleast_2d(np.asarray(model.G)).shape[1]
+    if nart and status in (L.OPTIMAL, L.UNBOUNDED):
+        bsum = 0.0
+        for v in xb:                                   # in row order, as the Big-M kernels add it
+            bsum += abs(float(v))
+        if attain[0] < -1e-9 * (bsum if bsum > 1.0 else 1.0):
+            status = L.INFEASIBLE
+    nan = float("nan")
+    sol = GoalSolution(L.STATUS_NAMES[status], np.full(n, nan), np.full(ng, nan), np.full(ng, nan), np.full(top, nan), pivots)
+    if status == L.OPTIMAL:
+        val = np.zeros(costs.shape[1] + 1)
+        for i in range(len(bas)):
+            val[bas[i]] = xb[i]
+        sol.x = val[1:1 + n].copy()
+        sol.under, sol.over = val[1 + n:1 + n + 2 * ng:2].copy(), val[2 + n:2 + n + 2 * ng:2].copy()
+        sol.attained = -np.asarray(attain[1 if nart else 0:], dtype=np.float64)
+    return sol
+
+
+@dataclass
 class AssignmentSolution:
     """solve_assignment's result for one cost matrix, in the caller's orientation."""
     status: str                  # OPTIMAL / INFEASIBLE

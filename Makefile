@@ -12,7 +12,7 @@ LIB       = linearprogramming_amd/liblpg.so
 
 OBJDIR    = build/obj
 KOBJS     = $(OBJDIR)/lpg_kernels.o $(OBJDIR)/lpg_block.o $(OBJDIR)/lpg_dual.o $(OBJDIR)/lpg_batch.o $(OBJDIR)/lpg_assign.o $(OBJDIR)/lpg_binary.o $(OBJDIR)/lpg_transport.o $(OBJDIR)/lpg_stamp.o
-HDRS      = $(CSRC)/lpg_internal.h $(CSRC)/lpg_device.h $(CSRC)/lpg_flushw.h include/lpg.h
+HDRS      = $(CSRC)/lpg_internal.h $(CSRC)/lpg_device.h $(CSRC)/lpg_flushw.h $(CSRC)/lpg_host.h include/lpg.h
 HOOKLIB   = linearprogramming_amd/liblpg_testhooks.so
 # the source stamp compiled into the library (lpg_build_stamp; _lib.load()
 # refuses a library whose stamp is not the sources')
@@ -58,13 +58,13 @@ ref:
 # phase-stamped build for tools/phase_probe.py and tools/block_probe.py
 # (diagnostics only; tools/probe/ travels to the GPU box, delete it when done)
 phases: tools/probe/liblpg_phases.so
-tools/probe/liblpg_phases.so: $(CSRC)/lpg_kernels.hip $(CSRC)/lpg_block.hip $(CSRC)/lpg_dual.hip $(CSRC)/lpg_batch.hip $(CSRC)/lpg_assign.hip $(CSRC)/lpg_binary.hip $(CSRC)/lpg_transport.hip $(CSRC)/lpg_ctx.hip $(CSRC)/lpg_internal.h $(CSRC)/lpg_device.h $(CSRC)/lpg_flushw.h $(OBJDIR)/lpg_stamp.o
+tools/probe/liblpg_phases.so: $(CSRC)/lpg_kernels.hip $(CSRC)/lpg_block.hip $(CSRC)/lpg_dual.hip $(CSRC)/lpg_batch.hip $(CSRC)/lpg_assign.hip $(CSRC)/lpg_binary.hip $(CSRC)/lpg_transport.hip $(CSRC)/lpg_ctx.hip $(HDRS) $(OBJDIR)/lpg_stamp.o
 	@mkdir -p tools/probe
 	$(HIPCC) $(HIPFLAGS) -DLPG_PHASES -shared -o $@ $(OBJDIR)/lpg_stamp.o $(CSRC)/lpg_kernels.hip $(CSRC)/lpg_block.hip $(CSRC)/lpg_dual.hip $(CSRC)/lpg_batch.hip $(CSRC)/lpg_assign.hip $(CSRC)/lpg_binary.hip $(CSRC)/lpg_transport.hip $(CSRC)/lpg_ctx.hip -ldl
 
 # publish / decision-seen stamps of every workgroup only (tools/block_probe.py PHASES_LIB=liblpg_pub.so)
 pub: tools/probe/liblpg_pub.so
-tools/probe/liblpg_pub.so: $(CSRC)/lpg_kernels.hip $(CSRC)/lpg_block.hip $(CSRC)/lpg_dual.hip $(CSRC)/lpg_batch.hip $(CSRC)/lpg_assign.hip $(CSRC)/lpg_binary.hip $(CSRC)/lpg_transport.hip $(CSRC)/lpg_ctx.hip $(CSRC)/lpg_internal.h $(CSRC)/lpg_device.h $(CSRC)/lpg_flushw.h $(OBJDIR)/lpg_stamp.o
+tools/probe/liblpg_pub.so: $(CSRC)/lpg_kernels.hip $(CSRC)/lpg_block.hip $(CSRC)/lpg_dual.hip $(CSRC)/lpg_batch.hip $(CSRC)/lpg_assign.hip $(CSRC)/lpg_binary.hip $(CSRC)/lpg_transport.hip $(CSRC)/lpg_ctx.hip $(HDRS) $(OBJDIR)/lpg_stamp.o
 	@mkdir -p tools/probe
 	$(HIPCC) $(HIPFLAGS) -DLPG_PHASES -DLPG_PHASES_PUBONLY -shared -o $@ $(OBJDIR)/lpg_stamp.o $(CSRC)/lpg_kernels.hip $(CSRC)/lpg_block.hip $(CSRC)/lpg_dual.hip $(CSRC)/lpg_batch.hip $(CSRC)/lpg_assign.hip $(CSRC)/lpg_binary.hip $(CSRC)/lpg_transport.hip $(CSRC)/lpg_ctx.hip -ldl
 

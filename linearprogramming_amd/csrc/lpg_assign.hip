@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -29,6 +28,7 @@
 #include "../../include/lpg.h"
 #include "lpg_internal.h"
 #include "lpg_device.h"
+#include "lpg_host.h"
 
 namespace lpg {
 
@@ -346,150 +346,56 @@ __global__ __launch_bounds__(kBlock) void k_assign_wg(AssignGeo g) {
 
 using namespace lpg;
 
-struct lpg_assign {
-    int device = 0;
-    int64_t count = 0, nr = 0, nc = 0;
+struct lpg_assign : BatchHost {
+    int64_t nr = 0, nc = 0;
     uint32_t flags = 0;
     int tier = LPG_BATCH_TIER_LDS, form = LPG_ASSIGN_FORM_WAVE;
-    int64_t lds = 0;
     bool state_lds = true;
     int64_t scratch_stride = 0;
-    bool on_device = false;       // the device side exists (made by the first call that needs it)
-    bool loaded = false;          // every problem has costs (a load of the whole range, or generate)
-    std::vector<uint8_t> have;    // per problem: loaded
-    bool solved = false;
-    bool lds_raised = false;
     double *C = nullptr, *u = nullptr, *v = nullptr;
     int32_t *col = nullptr;
     lpg_assign_result *res = nullptr;
     char *scratch = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;     // around the solve kernel
-    double kernel_ms = 0.0;
-    char err[512] = {0};
 };
 
 namespace {
 
-thread_local char g_aerr[512];
-
-int afail(lpg_assign *a, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (a) snprintf(a->err, sizeof a->err, "%s", buf);
-    snprintf(g_aerr, sizeof g_aerr, "%s", buf);
-    return code;
-}
-
-#define AHIPCHK(a, x)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            (void)hipGetLastError();                                                  \
-            return afail((a), LPG_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));   \
-        }                                                                             \
-    } while (0)
-
-bool env_is(const char *name, const char *value) {
-    const char *e = getenv(name);
-    return e && !strcmp(e, value);
-}
-
 // bytes of the column state of the workgroup form beyond kBlock columns: minv, v, then way, rowof, used
 int64_t state_bytes(int64_t nc) { return nc > kBlock ? ((2 * 8 + 3 * 4) * nc + 7) / 8 * 8 : 0; }
 
-// everything ensure_device made, whole or in part
-void release_device(lpg_assign *a) {
-    if (a->stream) (void)hipStreamSynchronize(a->stream);
-    for (void *p : {(void *)a->C, (void *)a->u, (void *)a->v, (void *)a->col, (void *)a->res, (void *)a->scratch})
-        if (p) (void)hipFree(p);
-    a->C = a->u = a->v = nullptr;
-    a->col = nullptr;
-    a->res = nullptr;
-    a->scratch = nullptr;
-    if (a->ev0) (void)hipEventDestroy(a->ev0);
-    if (a->ev1) (void)hipEventDestroy(a->ev1);
-    if (a->stream) (void)hipStreamDestroy(a->stream);
-    a->ev0 = a->ev1 = nullptr;
-    a->stream = nullptr;
-    a->on_device = false;
-}
-
-// Device memory, stream, events: made by the first call that moves data or
-// launches, so that every refusal of create, load, generate and solve is
-// answered before the library touches a device. A setup that fails is taken
-// down again, and the next call starts it afresh.
-int ensure_device(lpg_assign *a, const char *call) {
-    hipError_t e = hipSetDevice(a->device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return afail(a, LPG_ERR_DEVICE, "%s: hipSetDevice(%d): %s", call, a->device, hipGetErrorString(e));
-    }
-    if (a->on_device) return 0;
-    const size_t cb = (size_t)(a->count * a->nr * a->nc) * sizeof(double);
-    const size_t sb = a->state_lds ? 0 : (size_t)(a->count * a->scratch_stride);
-    if (hipMalloc(&a->C, cb) != hipSuccess || hipMalloc(&a->u, (size_t)(a->count * a->nr) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&a->v, (size_t)(a->count * a->nc) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&a->col, (size_t)(a->count * a->nr) * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&a->res, (size_t)a->count * sizeof(lpg_assign_result)) != hipSuccess ||
-        (sb && hipMalloc(&a->scratch, sb) != hipSuccess)) {
-        (void)hipGetLastError();
-        release_device(a);
-        return afail(a, LPG_ERR_OOM, "%s: hipMalloc(batch of %lld cost matrices, %zu bytes) failed", call,
-                     (long long)a->count, cb);
-    }
-    if ((e = hipStreamCreate(&a->stream)) != hipSuccess || (e = hipEventCreate(&a->ev0)) != hipSuccess ||
-        (e = hipEventCreate(&a->ev1)) != hipSuccess) {
-        (void)hipGetLastError();
-        release_device(a);
-        return afail(a, LPG_ERR_DEVICE, "%s: stream and events: %s", call, hipGetErrorString(e));
-    }
-    a->on_device = true;
-    return 0;
-}
-
-template <auto K>
-int launch_assign(lpg_assign *a, const AssignGeo &g, unsigned grid) {
-    if (!a->lds_raised) {
-        if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, kAssignMaxLds) != hipSuccess) {
-            (void)hipGetLastError();
-            return afail(a, LPG_ERR_DEVICE, "lpg_assign_solve: hipFuncSetAttribute(%d bytes of LDS) failed", kAssignMaxLds);
-        }
-        a->lds_raised = true;
-    }
-    (void)hipEventRecord(a->ev0, a->stream);
-    hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), (size_t)a->lds, a->stream, g);
-    (void)hipEventRecord(a->ev1, a->stream);
-    return 0;
+const void *solve_kernel(const lpg_assign *a) {
+    const bool reg = a->nc <= kBlock;
+    if (a->form == LPG_ASSIGN_FORM_WAVE) return (const void *)k_assign_wave;
+    if (a->tier == LPG_BATCH_TIER_LDS)
+        return reg ? (const void *)k_assign_wg<LPG_BATCH_TIER_LDS, true> : (const void *)k_assign_wg<LPG_BATCH_TIER_LDS, false>;
+    return reg ? (const void *)k_assign_wg<LPG_BATCH_TIER_GLOBAL, true> : (const void *)k_assign_wg<LPG_BATCH_TIER_GLOBAL, false>;
 }
 
 }  // namespace
 
 extern "C" {
 
-const char *lpg_assign_last_error(const lpg_assign *a) { return a ? a->err : g_aerr; }
+const char *lpg_assign_last_error(const lpg_assign *a) { return a ? a->err : thread_err<lpg_assign>(); }
 
 int lpg_assign_create(lpg_assign **out, int device, int64_t count, int64_t nr, int64_t nc, uint32_t flags) {
     const char *call = "lpg_assign_create";
-    if (!out) return afail(nullptr, LPG_ERR_ARG, "%s: out is NULL", call);
+    lpg_assign *a = nullptr;           // not made yet: the refusals below go to the thread's buffer only
+    if (!out) return fail(a, LPG_ERR_ARG, "%s: out is NULL", call);
     *out = nullptr;
     if (count < 1 || nr < 1 || nr > nc)
-        return afail(nullptr, LPG_ERR_ARG, "%s: bad shape count=%lld nr=%lld nc=%lld (need count >= 1 and 1 <= nr <= nc; "
-                                           "a matrix with more rows than columns is solved transposed)", call,
-                     (long long)count, (long long)nr, (long long)nc);
+        return fail(a, LPG_ERR_ARG, "%s: bad shape count=%lld nr=%lld nc=%lld (need count >= 1 and "
+                                    "1 <= nr <= nc; a matrix with more rows than columns is solved transposed)", call,
+                    (long long)count, (long long)nr, (long long)nc);
     if (nc > LPG_BATCH_MAX_DIM)
-        return afail(nullptr, LPG_ERR_ARG, "%s: nc = %lld exceeds LPG_BATCH_MAX_DIM = %d", call, (long long)nc,
-                     LPG_BATCH_MAX_DIM);
+        return fail(a, LPG_ERR_ARG, "%s: nc = %lld exceeds LPG_BATCH_MAX_DIM = %d", call, (long long)nc,
+                    LPG_BATCH_MAX_DIM);
     if (flags & ~(uint32_t)LPG_ASSIGN_MAXIMIZE)
-        return afail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_ASSIGN_MAXIMIZE only)", call, flags);
-    if (device < 0) return afail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+        return fail(a, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_ASSIGN_MAXIMIZE only)", call, flags);
+    if (device < 0) return fail(a, LPG_ERR_ARG, "%s: device %d", call, device);
     if (count > (int64_t)0x7fffffff / nr)
-        return afail(nullptr, LPG_ERR_ARG, "%s: count * nr = %lld x %lld exceeds 2^31 - 1", call, (long long)count,
-                     (long long)nr);
-    lpg_assign *a = new lpg_assign();
+        return fail(a, LPG_ERR_ARG, "%s: count * nr = %lld x %lld exceeds 2^31 - 1", call, (long long)count,
+                    (long long)nr);
+    a = new lpg_assign();
     a->device = device;
     a->count = count;
     a->nr = nr;
@@ -517,22 +423,20 @@ int lpg_assign_create(lpg_assign **out, int device, int64_t count, int64_t nr, i
             a->scratch_stride = a->state_lds ? 0 : sbytes;
         }
     }
+    const int64_t cb = count * nr * nc * (int64_t)sizeof(double);
+    a->allocs = {dev_array(a->C, count * nr * nc), dev_array(a->u, count * nr), dev_array(a->v, count * nc),
+                 dev_array(a->col, count * nr), dev_array(a->res, count),
+                 dev_array(a->scratch, a->state_lds ? 0 : count * a->scratch_stride)};
+    snprintf(a->oom_what, sizeof a->oom_what, "batch of %lld cost matrices, %zu bytes", (long long)count, (size_t)cb);
     *out = a;
     return 0;
 }
 
-void lpg_assign_destroy(lpg_assign *a) {
-    if (!a) return;
-    if (a->on_device) {
-        (void)hipSetDevice(a->device);
-        release_device(a);
-    }
-    delete a;
-}
+void lpg_assign_destroy(lpg_assign *a) { destroy(a); }
 
 int lpg_assign_info(const lpg_assign *a, lpg_assign_info_t *out) {
-    if (!a) return afail(nullptr, LPG_ERR_ARG, "lpg_assign_info: the batch is NULL");
-    if (!out) return afail(const_cast<lpg_assign *>(a), LPG_ERR_ARG, "lpg_assign_info: out is NULL");
+    if (!a) return fail<lpg_assign>(nullptr, LPG_ERR_ARG, "lpg_assign_info: the batch is NULL");
+    if (!out) return fail(const_cast<lpg_assign *>(a), LPG_ERR_ARG, "lpg_assign_info: out is NULL");
     out->count = a->count;
     out->nr = a->nr;
     out->nc = a->nc;
@@ -545,12 +449,10 @@ int lpg_assign_info(const lpg_assign *a, lpg_assign_info_t *out) {
 
 int lpg_assign_load(lpg_assign *a, int64_t first, int64_t n, const double *costs, int64_t ld) {
     const char *call = "lpg_assign_load";
-    if (!a) return afail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!costs) return afail(a, LPG_ERR_ARG, "%s: costs is NULL", call);
-    if (first < 0 || n < 1 || first > a->count || n > a->count - first)
-        return afail(a, LPG_ERR_ARG, "%s: problems [%lld, %lld) outside the batch of %lld (need n >= 1)", call,
-                     (long long)first, (long long)(first + n), (long long)a->count);
-    if (ld < a->nc) return afail(a, LPG_ERR_ARG, "%s: ld %lld < nc = %lld", call, (long long)ld, (long long)a->nc);
+    if (!a) return fail(a, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!costs) return fail(a, LPG_ERR_ARG, "%s: costs is NULL", call);
+    if (int rc = range_ok(a, call, first, n)) return rc;
+    if (ld < a->nc) return fail(a, LPG_ERR_ARG, "%s: ld %lld < nc = %lld", call, (long long)ld, (long long)a->nc);
     const int64_t nr = a->nr, nc = a->nc;
     const bool mx = (a->flags & LPG_ASSIGN_MAXIMIZE) != 0;
     std::vector<double> stage((size_t)(n * nr * nc));
@@ -560,47 +462,41 @@ int lpg_assign_load(lpg_assign *a, int64_t first, int64_t n, const double *costs
                 const double c = costs[(p * nr + i) * ld + j];
                 // +inf passes (a forbidden pair); NaN, -inf and |c| > the cap do not
                 if (!(c == INFINITY) && !(fabs(c) <= LPG_ASSIGN_COST_CAP))
-                    return afail(a, LPG_ERR_ARG, "%s: problem %lld, entry (%lld, %lld) is %s; costs are +inf (a forbidden "
-                                                 "pair) or finite with |c| <= 2^1000; nothing was loaded", call,
-                                 (long long)(first + p), (long long)i, (long long)j,
-                                 c != c ? "NaN" : c == -INFINITY ? "-inf" : "above the cap 2^1000 in magnitude");
+                    return fail(a, LPG_ERR_ARG, "%s: problem %lld, entry (%lld, %lld) is %s; costs are +inf (a forbidden "
+                                                "pair) or finite with |c| <= 2^1000; nothing was loaded", call,
+                                (long long)(first + p), (long long)i, (long long)j,
+                                c != c ? "NaN" : c == -INFINITY ? "-inf" : "above the cap 2^1000 in magnitude");
                 stage[(size_t)((p * nr + i) * nc + j)] = (mx && c != INFINITY) ? -c : c;
             }
     if (int rc = ensure_device(a, call)) return rc;
-    AHIPCHK(a, hipMemcpy(a->C + first * nr * nc, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
-    for (int64_t p = 0; p < n; p++) a->have[(size_t)(first + p)] = 1;
-    a->loaded = true;
-    for (uint8_t h : a->have) a->loaded = a->loaded && h;
+    LPG_HIPCHK(a, hipMemcpy(a->C + first * nr * nc, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+    mark_loaded(a, first, n);
     a->solved = false;
     return 0;
 }
 
 int lpg_assign_generate(lpg_assign *a, uint64_t seed, int64_t range) {
     const char *call = "lpg_assign_generate";
-    if (!a) return afail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!a) return fail(a, LPG_ERR_ARG, "%s: the batch is NULL", call);
     if (range < 1 || range > ((int64_t)1 << 53))
-        return afail(a, LPG_ERR_ARG, "%s: range %lld outside 1..2^53", call, (long long)range);
+        return fail(a, LPG_ERR_ARG, "%s: range %lld outside 1..2^53", call, (long long)range);
     if (int rc = ensure_device(a, call)) return rc;
     const int64_t per = a->nr * a->nc, total = a->count * per;
     hipLaunchKernelGGL(k_assign_generate, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, a->stream, a->C,
                        a->count, per, seed, (double)range, (a->flags & LPG_ASSIGN_MAXIMIZE) ? 1 : 0);
-    AHIPCHK(a, hipGetLastError());
-    AHIPCHK(a, hipStreamSynchronize(a->stream));
-    a->have.assign((size_t)a->count, 1);
-    a->loaded = true;
+    LPG_HIPCHK(a, hipGetLastError());
+    LPG_HIPCHK(a, hipStreamSynchronize(a->stream));
+    mark_all_loaded(a);
     a->solved = false;
     return 0;
 }
 
 int lpg_assign_solve(lpg_assign *a, lpg_assign_result *out) {
     const char *call = "lpg_assign_solve";
-    if (!a) return afail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!a->loaded) {
-        int64_t q = 0;
-        while (q < a->count && a->have[(size_t)q]) q++;
-        return afail(a, LPG_ERR_STATE, "%s: problem %lld has no costs yet (lpg_assign_load or lpg_assign_generate first)",
-                     call, (long long)q);
-    }
+    if (!a) return fail(a, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!a->loaded)
+        return fail(a, LPG_ERR_STATE, "%s: problem %lld has no costs yet (lpg_assign_load or lpg_assign_generate first)",
+                    call, (long long)first_unloaded(a));
     if (int rc = ensure_device(a, call)) return rc;
     AssignGeo g{};
     g.C = a->C;
@@ -618,43 +514,33 @@ int lpg_assign_solve(lpg_assign *a, lpg_assign_result *out) {
     // One launch, no chunk / relaunch scheme: row i's search marks a new column
     // used in every step and ends at the first free one, so it takes at most
     // i + 1 steps whatever the arithmetic does, nr (nr + 1) / 2 per problem.
-    int rc;
-    const bool lds = a->tier == LPG_BATCH_TIER_LDS, reg = a->nc <= kBlock;
-    if (a->form == LPG_ASSIGN_FORM_WAVE)
-        rc = launch_assign<k_assign_wave>(a, g, (unsigned)((a->count + kWaveProblems - 1) / kWaveProblems));
-    else if (lds)
-        rc = reg ? launch_assign<k_assign_wg<LPG_BATCH_TIER_LDS, true>>(a, g, (unsigned)a->count)
-                 : launch_assign<k_assign_wg<LPG_BATCH_TIER_LDS, false>>(a, g, (unsigned)a->count);
-    else
-        rc = reg ? launch_assign<k_assign_wg<LPG_BATCH_TIER_GLOBAL, true>>(a, g, (unsigned)a->count)
-                 : launch_assign<k_assign_wg<LPG_BATCH_TIER_GLOBAL, false>>(a, g, (unsigned)a->count);
-    if (rc) return rc;
-    AHIPCHK(a, hipGetLastError());
-    AHIPCHK(a, hipStreamSynchronize(a->stream));
+    const void *kern = solve_kernel(a);
+    const unsigned grid = (unsigned)(a->form == LPG_ASSIGN_FORM_WAVE ? (a->count + kWaveProblems - 1) / kWaveProblems : a->count);
+    if (int rc = raise_lds_once(a, kern, kAssignMaxLds, call)) return rc;
+    LPG_HIPCHK(a, timed_launch(a, kern, grid, g));
+    LPG_HIPCHK(a, hipStreamSynchronize(a->stream));
     a->solved = true;
     float ms = 0.0f;
-    AHIPCHK(a, hipEventElapsedTime(&ms, a->ev0, a->ev1));
+    LPG_HIPCHK(a, hipEventElapsedTime(&ms, a->ev0, a->ev1));
     a->kernel_ms = ms;
-    if (out) AHIPCHK(a, hipMemcpy(out, a->res, (size_t)a->count * sizeof(lpg_assign_result), hipMemcpyDeviceToHost));
+    if (out) LPG_HIPCHK(a, hipMemcpy(out, a->res, (size_t)a->count * sizeof(lpg_assign_result), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int lpg_assign_get(lpg_assign *a, int64_t first, int64_t n, int64_t *col, double *u, double *v) {
     const char *call = "lpg_assign_get";
-    if (!a) return afail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!col && !u && !v) return afail(a, LPG_ERR_ARG, "%s: col, u and v are all NULL", call);
-    if (first < 0 || n < 1 || first > a->count || n > a->count - first)
-        return afail(a, LPG_ERR_ARG, "%s: problems [%lld, %lld) outside the batch of %lld (need n >= 1)", call,
-                     (long long)first, (long long)(first + n), (long long)a->count);
-    if (!a->solved) return afail(a, LPG_ERR_STATE, "%s: no solve since the last load or generate", call);
-    AHIPCHK(a, hipSetDevice(a->device));
+    if (!a) return fail(a, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!col && !u && !v) return fail(a, LPG_ERR_ARG, "%s: col, u and v are all NULL", call);
+    if (int rc = range_ok(a, call, first, n)) return rc;
+    if (!a->solved) return fail(a, LPG_ERR_STATE, "%s: no solve since the last load or generate", call);
+    LPG_HIPCHK(a, hipSetDevice(a->device));
     if (col) {
         std::vector<int32_t> c32((size_t)(n * a->nr));
-        AHIPCHK(a, hipMemcpy(c32.data(), a->col + first * a->nr, c32.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        LPG_HIPCHK(a, hipMemcpy(c32.data(), a->col + first * a->nr, c32.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (size_t e = 0; e < c32.size(); e++) col[e] = c32[e];
     }
-    if (u) AHIPCHK(a, hipMemcpy(u, a->u + first * a->nr, (size_t)(n * a->nr) * sizeof(double), hipMemcpyDeviceToHost));
-    if (v) AHIPCHK(a, hipMemcpy(v, a->v + first * a->nc, (size_t)(n * a->nc) * sizeof(double), hipMemcpyDeviceToHost));
+    if (u) LPG_HIPCHK(a, hipMemcpy(u, a->u + first * a->nr, (size_t)(n * a->nr) * sizeof(double), hipMemcpyDeviceToHost));
+    if (v) LPG_HIPCHK(a, hipMemcpy(v, a->v + first * a->nc, (size_t)(n * a->nc) * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

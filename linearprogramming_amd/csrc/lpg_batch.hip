@@ -75,7 +75,6 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -87,6 +86,7 @@
 #include "../../include/lpg.h"
 #include "lpg_internal.h"
 #include "lpg_device.h"
+#include "lpg_host.h"
 
 namespace lpg {
 
@@ -1469,28 +1469,6 @@ constexpr int kBatchSlots = 2;                // ints behind lpg_batch::running:
 
 namespace {
 
-thread_local char g_berr[512];
-
-int bfail(lpg_batch *b, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (b) snprintf(b->err, sizeof b->err, "%s", buf);
-    snprintf(g_berr, sizeof g_berr, "%s", buf);
-    return code;
-}
-
-#define BHIPCHK(b, x)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            (void)hipGetLastError();                                                  \
-            return bfail((b), LPG_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));   \
-        }                                                                             \
-    } while (0)
-
 BatchGeo bgeo(const lpg_batch *b) {
     BatchGeo g{};
     g.T = b->T;
@@ -1535,8 +1513,8 @@ unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 int range_ok(lpg_batch *b, const char *what, int64_t first, int64_t n) {
     if (first < 0 || n < 0 || first > b->count || n > b->count - first)
-        return bfail(b, LPG_ERR_ARG, "%s: LPs [%lld, %lld) outside the batch of %lld", what, (long long)first,
-                     (long long)(first + n), (long long)b->count);
+        return fail(b, LPG_ERR_ARG, "%s: LPs [%lld, %lld) outside the batch of %lld", what, (long long)first,
+                    (long long)(first + n), (long long)b->count);
     return 0;
 }
 
@@ -1551,7 +1529,7 @@ int alloc_log(lpg_batch *b, int64_t cap) {
         (void)hipGetLastError();
         if (b->logk) (void)hipFree(b->logk);
         b->logk = b->logr = nullptr;
-        return bfail(b, LPG_ERR_OOM, "hipMalloc(pivot log, 2 x %zu bytes) failed", bytes);
+        return fail(b, LPG_ERR_OOM, "hipMalloc(pivot log, 2 x %zu bytes) failed", bytes);
     }
     b->logcap = cap;
     return 0;
@@ -1568,7 +1546,7 @@ int raise_lds(lpg_batch *b, const char *name, int bytes = kBatchMaxLds) {
     if (!((attr.load(std::memory_order_acquire) >> dev) & 1ull)) {
         if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
             (void)hipGetLastError();
-            return bfail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(%s, %d bytes of LDS) failed", name, bytes);
+            return fail(b, LPG_ERR_DEVICE, "hipFuncSetAttribute(%s, %d bytes of LDS) failed", name, bytes);
         }
         attr.fetch_or(1ull << dev, std::memory_order_acq_rel);
     }
@@ -1623,10 +1601,10 @@ int launch_solve(lpg_batch *b, const lpg_batch::Group &gr, Method method, int ru
 // batch, or a packed / _ragged call on a batch of one shape
 int wrong_layout(lpg_batch *b, const char *call, const char *other) {
     if (b->ragged)
-        return bfail(b, LPG_ERR_STATE, "%s: this is a ragged batch (lpg_batch_create_ragged), whose LPs have no common "
-                                       "shape; use %s; nothing has moved or pivoted", call, other);
-    return bfail(b, LPG_ERR_STATE, "%s: this batch has one shape (lpg_batch_create, lpg_batch_create_big_m); use %s; "
-                                   "nothing has moved or pivoted", call, other);
+        return fail(b, LPG_ERR_STATE, "%s: this is a ragged batch (lpg_batch_create_ragged), whose LPs have no common "
+                                      "shape; use %s; nothing has moved or pivoted", call, other);
+    return fail(b, LPG_ERR_STATE, "%s: this batch has one shape (lpg_batch_create, lpg_batch_create_big_m); use %s; "
+                                  "nothing has moved or pivoted", call, other);
 }
 
 // a plain batch: neither Big-M nor goal
@@ -1635,14 +1613,14 @@ bool plain(const lpg_batch *b) { return b->nobj == 1 && !b->goal; }
 // what a Big-M batch and a goal batch refuse (and a plain batch, for lpg_batch_solve_big_m)
 int wrong_kind(lpg_batch *b, const char *call) {
     if (b->goal)
-        return bfail(b, LPG_ERR_STATE, "%s: this is a goal batch (lpg_batch_create_goal, %d objective rows); only "
-                                       "lpg_batch_solve_goal pivots it, and lpg_batch_load, _get_rows, _get_basis, _get_log, "
-                                       "_info and _set_tolerances serve it; nothing has moved or pivoted", call, b->nobj);
+        return fail(b, LPG_ERR_STATE, "%s: this is a goal batch (lpg_batch_create_goal, %d objective rows); only "
+                                      "lpg_batch_solve_goal pivots it, and lpg_batch_load, _get_rows, _get_basis, _get_log, "
+                                      "_info and _set_tolerances serve it; nothing has moved or pivoted", call, b->nobj);
     if (b->nobj == 2)
-        return bfail(b, LPG_ERR_STATE, "%s: this is a Big-M batch (lpg_batch_create_big_m, two objective rows); only "
-                                       "lpg_batch_solve_big_m pivots it; nothing has pivoted", call);
-    return bfail(b, LPG_ERR_STATE, "%s: the batch has one objective row (lpg_batch_create); Big-M needs a batch from "
-                                   "lpg_batch_create_big_m; nothing has pivoted", call);
+        return fail(b, LPG_ERR_STATE, "%s: this is a Big-M batch (lpg_batch_create_big_m, two objective rows); only "
+                                      "lpg_batch_solve_big_m pivots it; nothing has pivoted", call);
+    return fail(b, LPG_ERR_STATE, "%s: the batch has one objective row (lpg_batch_create); Big-M needs a batch from "
+                                  "lpg_batch_create_big_m; nothing has pivoted", call);
 }
 
 // the batch's count x N cost buffer, filled from the host's (pitch ld_cost) when given;
@@ -1653,33 +1631,33 @@ int stage_costs(lpg_batch *b, const double *cost, int64_t ld_cost) {
     if (!b->cost && hipMalloc(&b->cost, total * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         b->cost = nullptr;
-        return bfail(b, LPG_ERR_OOM, "hipMalloc(costs of %lld LPs) failed", (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "hipMalloc(costs of %lld LPs) failed", (long long)b->count);
     }
     if (cost && b->ragged)
-        BHIPCHK(b, hipMemcpyAsync(b->cost, cost, total * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        LPG_HIPCHK(b, hipMemcpyAsync(b->cost, cost, total * sizeof(double), hipMemcpyHostToDevice, b->stream));
     else if (cost)
-        BHIPCHK(b, hipMemcpy2DAsync(b->cost, (size_t)N * sizeof(double), cost, (size_t)ld_cost * sizeof(double),
+        LPG_HIPCHK(b, hipMemcpy2DAsync(b->cost, (size_t)N * sizeof(double), cost, (size_t)ld_cost * sizeof(double),
                                     (size_t)N * sizeof(double), (size_t)b->count, hipMemcpyHostToDevice, b->stream));
-    if (cost) BHIPCHK(b, hipStreamSynchronize(b->stream));        // the caller's array is free again
+    if (cost) LPG_HIPCHK(b, hipStreamSynchronize(b->stream));        // the caller's array is free again
     return 0;
 }
 
 // one solve call: `method` with `rule` (M_DUAL: RULE_DANTZIG); `t` for M_TWO_PHASE and M_BIG_M
 int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_result *out, const TwoPhase &t = {}) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
-    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "max_pivots < 0");
-    BHIPCHK(b, hipSetDevice(b->device));
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (max_pivots < 0) return fail(b, LPG_ERR_ARG, "max_pivots < 0");
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     if (method == M_DUAL) {
         const unsigned long long none = ~0ull;
         unsigned long long bad = none;
-        BHIPCHK(b, hipMemcpyAsync(b->bad, &none, sizeof none, hipMemcpyHostToDevice, b->stream));
+        LPG_HIPCHK(b, hipMemcpyAsync(b->bad, &none, sizeof none, hipMemcpyHostToDevice, b->stream));
         hipLaunchKernelGGL(k_batch_dual_check, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b), b->bad);
-        BHIPCHK(b, hipGetLastError());
-        BHIPCHK(b, hipMemcpyAsync(&bad, b->bad, sizeof bad, hipMemcpyDeviceToHost, b->stream));
-        BHIPCHK(b, hipStreamSynchronize(b->stream));
+        LPG_HIPCHK(b, hipGetLastError());
+        LPG_HIPCHK(b, hipMemcpyAsync(&bad, b->bad, sizeof bad, hipMemcpyDeviceToHost, b->stream));
+        LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
         if (bad != none)
-            return bfail(b, LPG_ERR_STATE, "lpg_batch_solve_dual: LP %llu is not dual feasible (a d_j < -eps_opt); "
-                                           "nothing has pivoted", bad);
+            return fail(b, LPG_ERR_STATE, "lpg_batch_solve_dual: LP %llu is not dual feasible (a d_j < -eps_opt); "
+                                          "nothing has pivoted", bad);
     }
     // every launch spends `chunk` of each running LP's budget (or ends the LP)
     int64_t max_launches = max_pivots / b->chunk + 2;
@@ -1696,31 +1674,31 @@ int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_res
     else
         hipLaunchKernelGGL(k_batch_begin, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, b->count,
                            max_pivots, method == M_DUAL ? 1 : 0);
-    BHIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipGetLastError());
     b->pivoted = true;
     // a round: one launch per group that still has running LPs; the counters are
     // reset once before it and read once after it
     int32_t live[kBatchSlots];
     const size_t nslots = (size_t)b->groups.back().slot + 1;
     for (int64_t it = 0;; it++) {
-        BHIPCHK(b, hipMemsetAsync(b->running, 0, nslots * sizeof(int32_t), b->stream));
+        LPG_HIPCHK(b, hipMemsetAsync(b->running, 0, nslots * sizeof(int32_t), b->stream));
         for (const lpg_batch::Group &gr : b->groups) {
             if (it > 0 && live[gr.slot] == 0) continue;
             if (int rc = launch_solve(b, gr, method, rule, t)) return rc;
-            BHIPCHK(b, hipGetLastError());
+            LPG_HIPCHK(b, hipGetLastError());
         }
-        BHIPCHK(b, hipMemcpyAsync(live, b->running, nslots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-        BHIPCHK(b, hipStreamSynchronize(b->stream));
+        LPG_HIPCHK(b, hipMemcpyAsync(live, b->running, nslots * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+        LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
         int64_t running = 0;
         for (size_t q = 0; q < nslots; q++) running += live[q];
         if (running == 0) break;
         if (it + 1 >= max_launches)
-            return bfail(b, LPG_ERR_DEVICE, "lpg_batch: %lld LPs still running after %lld rounds of %d pivots",
-                         (long long)running, (long long)(it + 1), b->chunk);
+            return fail(b, LPG_ERR_DEVICE, "lpg_batch: %lld LPs still running after %lld rounds of %d pivots",
+                        (long long)running, (long long)(it + 1), b->chunk);
     }
     if (out) {
         std::vector<BatchLP> h((size_t)b->count);
-        BHIPCHK(b, hipMemcpy(h.data(), b->lp, h.size() * sizeof(BatchLP), hipMemcpyDeviceToHost));
+        LPG_HIPCHK(b, hipMemcpy(h.data(), b->lp, h.size() * sizeof(BatchLP), hipMemcpyDeviceToHost));
         for (int64_t q = 0; q < b->count; q++) {
             out[q].status = h[q].status;
             out[q].rule = rule == RULE_BLAND ? LPG_RULE_BLAND : LPG_RULE_DANTZIG;
@@ -1735,7 +1713,7 @@ int batch_run(lpg_batch *b, int64_t max_pivots, Method method, int rule, lpg_res
 
 // the records of a ragged batch to the device (after nact or art_first changed)
 int push_shapes(lpg_batch *b) {
-    BHIPCHK(b, hipMemcpy(b->dshape, b->shape.data(), b->shape.size() * sizeof(BatchShape), hipMemcpyHostToDevice));
+    LPG_HIPCHK(b, hipMemcpy(b->dshape, b->shape.data(), b->shape.size() * sizeof(BatchShape), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1744,7 +1722,7 @@ int push_shapes(lpg_batch *b) {
 // `call` names the entry point
 int solve_artificial(lpg_batch *b, Method method, const char *call, bool packed, const int64_t *art_first,
                      const double *cost, int64_t ld_cost, int64_t max_pivots, int rule, lpg_result *out) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (b->goal || (b->nobj == 2) != (method == M_BIG_M)) return wrong_kind(b, call);
     if (b->ragged != packed) {
         if (packed) return wrong_layout(b, call, method == M_BIG_M ? "lpg_batch_solve_big_m" : "lpg_batch_solve_two_phase");
@@ -1752,19 +1730,19 @@ int solve_artificial(lpg_batch *b, Method method, const char *call, bool packed,
     }
     const int64_t N = b->ncols - 1;
     if (packed) {
-        if (!art_first) return bfail(b, LPG_ERR_ARG, "%s: art_first is NULL", call);
+        if (!art_first) return fail(b, LPG_ERR_ARG, "%s: art_first is NULL", call);
         for (int64_t q = 0; q < b->count; q++)
             if (art_first[q] < 2 || art_first[q] > b->shape[(size_t)q].ncols - 1)
-                return bfail(b, LPG_ERR_ARG, "%s: art_first %lld of LP %lld outside 2..%lld", call, (long long)art_first[q],
-                             (long long)q, (long long)(b->shape[(size_t)q].ncols - 1));
+                return fail(b, LPG_ERR_ARG, "%s: art_first %lld of LP %lld outside 2..%lld", call, (long long)art_first[q],
+                            (long long)q, (long long)(b->shape[(size_t)q].ncols - 1));
     } else if (*art_first < 2 || *art_first > N) {
-        return bfail(b, LPG_ERR_ARG, "%s: art_first %lld outside 2..%lld", call, (long long)*art_first, (long long)N);
+        return fail(b, LPG_ERR_ARG, "%s: art_first %lld outside 2..%lld", call, (long long)*art_first, (long long)N);
     }
-    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return fail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
     if (!packed && cost && ld_cost < N)
-        return bfail(b, LPG_ERR_ARG, "%s: ld_cost %lld < N = %lld", call, (long long)ld_cost, (long long)N);
-    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
-    BHIPCHK(b, hipSetDevice(b->device));
+        return fail(b, LPG_ERR_ARG, "%s: ld_cost %lld < N = %lld", call, (long long)ld_cost, (long long)N);
+    if (max_pivots < 0) return fail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     if (int rc = stage_costs(b, cost, ld_cost)) return rc;
     TwoPhase t{};
     t.cost = b->cost;
@@ -1786,12 +1764,12 @@ int solve_artificial(lpg_batch *b, Method method, const char *call, bool packed,
 
 // lpg_batch_generate and lpg_batch_generate_artificial once the arguments are checked
 int generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     hipLaunchKernelGGL(k_batch_generate, dim3((unsigned)(b->count * (b->m + b->nobj))), dim3(kBlock), 0, b->stream, bgeo(b),
                        n, seed, kind);
     hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     b->pivoted = false;
     return 0;
 }
@@ -1802,15 +1780,10 @@ int env_chunk(int *chunk) {
     if (const char *ce = getenv("LPG_BATCH_CHUNK")) {
         const long long v = atoll(ce);
         if (v < 1 || v > (1 << 20))
-            return bfail(nullptr, LPG_ERR_ARG, "LPG_BATCH_CHUNK=%s out of range [1, %d]", ce, 1 << 20);
+            return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "LPG_BATCH_CHUNK=%s out of range [1, %d]", ce, 1 << 20);
         *chunk = (int)v;
     }
     return 0;
-}
-
-bool env_is(const char *name, const char *value) {
-    const char *e = getenv(name);
-    return e && !strcmp(e, value);
 }
 
 // a launch stays bounded in time as well as in pivots: the LDS tier spends
@@ -1835,7 +1808,7 @@ int txs_of(int64_t ncols) {
 // bases, fresh states. On failure the batch is destroyed.
 int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector<int32_t> &order) {
     auto die = [&](int code) {
-        snprintf(g_berr, sizeof g_berr, "%s", b->err);
+        snprintf(thread_err<lpg_batch>(), kErrLen, "%s", b->err);
         lpg_batch_destroy(b);
         return code;
     };
@@ -1843,7 +1816,7 @@ int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector
     hipError_t e = hipSetDevice(b->device);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipSetDevice(%d): %s", b->device, hipGetErrorString(e));
+        fail(b, LPG_ERR_DEVICE, "hipSetDevice(%d): %s", b->device, hipGetErrorString(e));
         return die(LPG_ERR_DEVICE);
     }
     const size_t tbytes = (size_t)b->t_total * sizeof(double), bbytes = (size_t)b->b_total * sizeof(int64_t);
@@ -1854,19 +1827,19 @@ int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector
         (b->ragged && (hipMalloc(&b->dshape, (size_t)count * sizeof(BatchShape)) != hipSuccess ||
                        hipMalloc(&b->dorder, (size_t)count * sizeof(int32_t)) != hipSuccess))) {
         (void)hipGetLastError();
-        bfail(b, LPG_ERR_OOM, "hipMalloc(batch of %lld tableaus, %zu bytes) failed", (long long)count, tbytes);
+        fail(b, LPG_ERR_OOM, "hipMalloc(batch of %lld tableaus, %zu bytes) failed", (long long)count, tbytes);
         return die(LPG_ERR_OOM);
     }
     if (int rc = alloc_log(b, logcap)) return die(rc);
     if ((e = hipStreamCreate(&b->stream)) != hipSuccess) {
         (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
+        fail(b, LPG_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
         return die(LPG_ERR_DEVICE);
     }
     if (hipMemsetAsync(b->T, 0, tbytes, b->stream) != hipSuccess ||
         hipMemsetAsync(b->basis, 0, bbytes, b->stream) != hipSuccess) {
         (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipMemset failed");
+        fail(b, LPG_ERR_DEVICE, "hipMemset failed");
         return die(LPG_ERR_DEVICE);
     }
     if (b->ragged &&
@@ -1875,12 +1848,12 @@ int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector
          hipMemcpyAsync(b->dorder, order.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, b->stream) !=
              hipSuccess)) {
         (void)hipGetLastError();
-        bfail(b, LPG_ERR_DEVICE, "hipMemcpy(shapes of %lld LPs) failed", (long long)count);
+        fail(b, LPG_ERR_DEVICE, "hipMemcpy(shapes of %lld LPs) failed", (long long)count);
         return die(LPG_ERR_DEVICE);
     }
     hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, count);
     if ((e = hipStreamSynchronize(b->stream)) != hipSuccess || (e = hipGetLastError()) != hipSuccess) {
-        bfail(b, LPG_ERR_DEVICE, "batch setup: %s", hipGetErrorString(e));
+        fail(b, LPG_ERR_DEVICE, "batch setup: %s", hipGetErrorString(e));
         return die(LPG_ERR_DEVICE);
     }
     *out = b;
@@ -1891,23 +1864,23 @@ int batch_alloc(lpg_batch **out, lpg_batch *b, int64_t logcap, const std::vector
 // `call` names the entry point
 int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags, int nobj,
                  const char *call, bool goal = false) {
-    if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
+    if (!out) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (count < 1 || m < 1 || ncols < 2)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: bad shape count=%lld m=%lld ncols=%lld (need count >= 1, "
-                                           "m >= 1, ncols >= 2)", call, (long long)count, (long long)m, (long long)ncols);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: bad shape count=%lld m=%lld ncols=%lld (need count >= 1, "
+                                                     "m >= 1, ncols >= 2)", call, (long long)count, (long long)m, (long long)ncols);
     if (flags & ~(uint32_t)LPG_FLAG_NO_LOG)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_FLAG_NO_LOG only: a Big-M batch comes from "
-                                           "lpg_batch_create_big_m; no eager or no-skip batches)", call, flags);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_FLAG_NO_LOG only: a Big-M batch comes from "
+                                                     "lpg_batch_create_big_m; no eager or no-skip batches)", call, flags);
     if (m + nobj > LPG_BATCH_MAX_DIM || ncols > LPG_BATCH_MAX_DIM)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: m + %d = %lld, ncols = %lld exceed %d; a tableau this large "
-                                           "belongs to lpg_create", call, nobj, (long long)(m + nobj), (long long)ncols,
-                     LPG_BATCH_MAX_DIM);
-    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: m + %d = %lld, ncols = %lld exceed %d; a tableau this large "
+                                                     "belongs to lpg_create", call, nobj, (long long)(m + nobj), (long long)ncols,
+                               LPG_BATCH_MAX_DIM);
+    if (device < 0) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
     const int64_t rows = m + nobj, ld = (ncols + 63) & ~(int64_t)63;   // the engine's padded pitch (512-byte rows)
     if (count > (int64_t)0x7fffffff / rows)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: count * (m + %d) = %lld x %lld exceeds 2^31 - 1", call, nobj,
-                     (long long)count, (long long)rows);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: count * (m + %d) = %lld x %lld exceeds 2^31 - 1", call, nobj,
+                               (long long)count, (long long)rows);
     int chunk = 0;
     if (int rc = env_chunk(&chunk)) return rc;
     lpg_batch *b = new lpg_batch();
@@ -1935,32 +1908,35 @@ int batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t 
 int ragged_create(lpg_batch **out, int device, int64_t count, const int64_t *m, const int64_t *ncols, int nobj,
                   uint32_t flags) {
     const char *call = "lpg_batch_create_ragged";
-    if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
+    if (!out) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "out is NULL");
     *out = nullptr;
-    if (!m || !ncols) return bfail(nullptr, LPG_ERR_ARG, "%s: %s is NULL", call, !m ? "m" : "ncols");
-    if (count < 1) return bfail(nullptr, LPG_ERR_ARG, "%s: count = %lld (need count >= 1)", call, (long long)count);
+    if (!m || !ncols) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: %s is NULL", call, !m ? "m" : "ncols");
+    if (count < 1) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: count = %lld (need count >= 1)", call, (long long)count);
     if (nobj != 1 && nobj != 2)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: nobj = %d (1: a plain batch, 2: a Big-M batch)", call, nobj);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: nobj = %d (1: a plain batch, 2: a Big-M batch)", call, nobj);
     if (flags & ~(uint32_t)LPG_FLAG_NO_LOG)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_FLAG_NO_LOG only: nobj = 2 makes a Big-M "
-                                           "batch; no eager or no-skip batches)", call, flags);
-    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_FLAG_NO_LOG only: nobj = 2 makes a Big-M "
+                                                     "batch; no eager or no-skip batches)", call, flags);
+    if (device < 0) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
     int64_t sum_rows = 0;
     for (int64_t q = 0; q < count; q++) {
-        if (m[q] < 1) return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: m = %lld (need m >= 1)", call, (long long)q, (long long)m[q]);
+        if (m[q] < 1)
+            return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: LP %lld: m = %lld (need m >= 1)", call, (long long)q,
+                                   (long long)m[q]);
         if (ncols[q] < 2)
-            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: ncols = %lld (need ncols >= 2)", call, (long long)q,
-                         (long long)ncols[q]);
+            return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: LP %lld: ncols = %lld (need ncols >= 2)", call, (long long)q,
+                                   (long long)ncols[q]);
         if (m[q] + nobj > LPG_BATCH_MAX_DIM)
-            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: m + %d = %lld exceeds %d; a tableau this large belongs to "
-                                               "lpg_create", call, (long long)q, nobj, (long long)(m[q] + nobj), LPG_BATCH_MAX_DIM);
+            return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: LP %lld: m + %d = %lld exceeds %d; a tableau this large belongs to "
+                                                         "lpg_create", call, (long long)q, nobj, (long long)(m[q] + nobj),
+                                   LPG_BATCH_MAX_DIM);
         if (ncols[q] > LPG_BATCH_MAX_DIM)
-            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: ncols = %lld exceeds %d; a tableau this large belongs to "
-                                               "lpg_create", call, (long long)q, (long long)ncols[q], LPG_BATCH_MAX_DIM);
+            return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: LP %lld: ncols = %lld exceeds %d; a tableau this large belongs to "
+                                                         "lpg_create", call, (long long)q, (long long)ncols[q], LPG_BATCH_MAX_DIM);
         sum_rows += m[q] + nobj;
         if (sum_rows > (int64_t)0x7fffffff)
-            return bfail(nullptr, LPG_ERR_ARG, "%s: LP %lld: the rows of LPs 0..%lld (m + %d each) exceed 2^31 - 1", call,
-                         (long long)q, (long long)q, nobj);
+            return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: LP %lld: the rows of LPs 0..%lld (m + %d each) exceed 2^31 - 1", call,
+                                   (long long)q, (long long)q, nobj);
     }
     int chunk = 0;
     if (int rc = env_chunk(&chunk)) return rc;
@@ -2052,11 +2028,11 @@ struct DevBuf {
 // the mask checks of the calls that take one, once the batch is known
 int mask_ok(lpg_batch *b, const char *call, int64_t nmask, int64_t ld_mask) {
     if (nmask < 1 || nmask > b->ncols - 1)
-        return bfail(b, LPG_ERR_ARG, "%s: nmask %lld outside 1..%lld (the columns of the %s)", call, (long long)nmask,
-                     (long long)(b->ncols - 1), b->ragged ? "widest LP" : "batch");
+        return fail(b, LPG_ERR_ARG, "%s: nmask %lld outside 1..%lld (the columns of the %s)", call, (long long)nmask,
+                    (long long)(b->ncols - 1), b->ragged ? "widest LP" : "batch");
     if (ld_mask != 0 && ld_mask < nmask)
-        return bfail(b, LPG_ERR_ARG, "%s: ld_mask %lld < nmask %lld (0: one mask for every LP)", call, (long long)ld_mask,
-                     (long long)nmask);
+        return fail(b, LPG_ERR_ARG, "%s: ld_mask %lld < nmask %lld (0: one mask for every LP)", call, (long long)ld_mask,
+                    (long long)nmask);
     return 0;
 }
 
@@ -2075,14 +2051,14 @@ hipError_t stage_mask(DevBuf &dmask, int64_t &pitch, const uint8_t *mask, int64_
 // src[c] of lpg_batch_branch and lpg_batch_cut names an LP of the parent
 int src_ok(lpg_batch *p, const char *call, int64_t c, int64_t src) {
     if (src < 0 || src >= p->count)
-        return bfail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c, (long long)src,
-                     (long long)(p->count - 1));
+        return fail(p, LPG_ERR_ARG, "%s: src[%lld] = %lld outside the parent's LPs 0..%lld", call, (long long)c, (long long)src,
+                    (long long)(p->count - 1));
     return 0;
 }
 
 // a child batch that will not be returned: its message to the parent and the thread, and away with it
 int child_die(lpg_batch *p, lpg_batch *ch, int code) {
-    snprintf(g_berr, sizeof g_berr, "%s", ch->err);
+    snprintf(thread_err<lpg_batch>(), kErrLen, "%s", ch->err);
     snprintf(p->err, sizeof p->err, "%s", ch->err);
     lpg_batch_destroy(ch);
     return code;
@@ -2102,7 +2078,7 @@ int grow_create(lpg_batch **out, lpg_batch *p, const char *call, int64_t n, cons
     } else {
         rc = batch_create(&ch, p->device, n, p->m + k[0], p->ncols + k[0], p->flags, 1, call);
     }
-    if (rc) return bfail(p, rc, "%s: the child batch: %s", call, g_berr);
+    if (rc) return fail(p, rc, "%s: the child batch: %s", call, thread_err<lpg_batch>());
     ch->eps_piv = p->eps_piv;
     ch->eps_opt = p->eps_opt;
     if (ragged) {
@@ -2137,7 +2113,7 @@ int grow_finish(lpg_batch **out, lpg_batch *p, lpg_batch *ch, const char *call, 
     if (e == hipSuccess) e = hipStreamSynchronize(ch->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        bfail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
+        fail(ch, LPG_ERR_DEVICE, "%s: %s", call, hipGetErrorString(e));
         return child_die(p, ch, LPG_ERR_DEVICE);
     }
     *out = ch;
@@ -2163,8 +2139,8 @@ int ident_ok(lpg_batch *b, const char *call, const int64_t *ident) {
     for (int64_t q = 0, at = 0; q < b->count; q++)
         for (int64_t i = 0, m = lp_m(b, q), N = lp_ncols(b, q) - 1; i < m; i++, at++)
             if (ident[at] < 1 || ident[at] > N)
-                return bfail(b, LPG_ERR_ARG, "%s: ident[%lld] = %lld (row %lld of LP %lld) outside the columns 1..%lld", call,
-                             (long long)at, (long long)ident[at], (long long)i, (long long)q, (long long)N);
+                return fail(b, LPG_ERR_ARG, "%s: ident[%lld] = %lld (row %lld of LP %lld) outside the columns 1..%lld", call,
+                            (long long)at, (long long)ident[at], (long long)i, (long long)q, (long long)N);
     return 0;
 }
 
@@ -2172,8 +2148,8 @@ int ident_ok(lpg_batch *b, const char *call, const int64_t *ident) {
 int rhs_ok(lpg_batch *b, const char *call, const double *rhs, int64_t at, int64_t m, const char *whose, int64_t q) {
     for (int64_t i = 0; i < m; i++)
         if (!std::isfinite(rhs[at + i]))
-            return bfail(b, LPG_ERR_ARG, "%s: rhs[%lld] = %g (row %lld of %s %lld) is not finite", call, (long long)(at + i),
-                         rhs[at + i], (long long)i, whose, (long long)q);
+            return fail(b, LPG_ERR_ARG, "%s: rhs[%lld] = %g (row %lld of %s %lld) is not finite", call, (long long)(at + i),
+                        rhs[at + i], (long long)i, whose, (long long)q);
     return 0;
 }
 
@@ -2183,13 +2159,13 @@ extern "C" {
 
 int lpg_batch_scenario(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *ident, const double *rhs) {
     const char *call = "lpg_batch_scenario";
-    if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
+    if (!out) return fail(p, LPG_ERR_ARG, "%s: child is NULL", call);
     *out = nullptr;
     // what does not depend on the parent first
-    if (n < 1) return bfail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
+    if (n < 1) return fail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
     if (!src || !ident || !rhs)
-        return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !ident ? "ident" : "rhs");
-    if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
+        return fail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !ident ? "ident" : "rhs");
+    if (!p) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
     if (!plain(p)) return wrong_kind(p, call);
     for (int64_t c = 0; c < n; c++)
         if (int rc = src_ok(p, call, c, src[c])) return rc;
@@ -2212,7 +2188,7 @@ int lpg_batch_scenario(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *
     if (hipMalloc(&djobs.p, jobs.size() * sizeof(ScenarioJob)) != hipSuccess || hipMalloc(&dident.p, ibytes) != hipSuccess ||
         hipMalloc(&drhs.p, rbytes) != hipSuccess) {
         (void)hipGetLastError();
-        bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, ident, %lld right-hand sides) failed", call, (long long)n, (long long)at);
+        fail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, ident, %lld right-hand sides) failed", call, (long long)n, (long long)at);
         return child_die(p, ch, LPG_ERR_OOM);
     }
     hipError_t e = hipMemcpyAsync(dident.p, ident, ibytes, hipMemcpyHostToDevice, ch->stream);
@@ -2224,27 +2200,27 @@ int lpg_batch_scenario(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *
 
 int lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs) {
     const char *call = "lpg_batch_set_rhs";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
-    if (!ident || !rhs) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !ident ? "ident" : "rhs");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (!ident || !rhs) return fail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !ident ? "ident" : "rhs");
     if (!plain(b)) return wrong_kind(b, call);
     if (int rc = ident_ok(b, call, ident)) return rc;
     for (int64_t q = 0, at = 0; q < b->count; at += lp_m(b, q), q++)
         if (int rc = rhs_ok(b, call, rhs, at, lp_m(b, q), "LP", q)) return rc;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     if (int rc = raise_lds<k_batch_set_rhs>(b, "k_batch_set_rhs", kScenarioMaxLds)) return rc;
     DevBuf dident, drhs;
     if (hipMalloc(&dident.p, (size_t)b->b_total * sizeof(int64_t)) != hipSuccess ||
         hipMalloc(&drhs.p, (size_t)b->b_total * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
-        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(ident and right-hand sides of %lld LPs) failed", call, (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "%s: hipMalloc(ident and right-hand sides of %lld LPs) failed", call, (long long)b->count);
     }
-    BHIPCHK(b, hipMemcpyAsync(dident.p, ident, (size_t)b->b_total * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
-    BHIPCHK(b, hipMemcpyAsync(drhs.p, rhs, (size_t)b->b_total * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(dident.p, ident, (size_t)b->b_total * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(drhs.p, rhs, (size_t)b->b_total * sizeof(double), hipMemcpyHostToDevice, b->stream));
     hipLaunchKernelGGL(k_batch_set_rhs, dim3((unsigned)b->count), dim3(kBlock), scenario_lds(b->m), b->stream, bgeo(b),
                        (const int64_t *)dident.p, (const double *)drhs.p, scenario_walk());
     hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(b->count)), dim3(kBlock), 0, b->stream, b->lp, (int64_t)0, b->count);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     b->pivoted = false;
     return 0;
 }
@@ -2252,21 +2228,21 @@ int lpg_batch_set_rhs(lpg_batch *b, const int64_t *ident, const double *rhs) {
 int lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *out) {
     const char *call = "lpg_batch_ranging";
     // what does not depend on the batch first
-    if (!out) return bfail(b, LPG_ERR_ARG, "%s: out is NULL", call);
-    if (!ident) return bfail(b, LPG_ERR_ARG, "%s: ident is NULL", call);
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (!out) return fail(b, LPG_ERR_ARG, "%s: out is NULL", call);
+    if (!ident) return fail(b, LPG_ERR_ARG, "%s: ident is NULL", call);
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
     const int ncost = !!out->cost_lo + !!out->cost_hi + !!out->cost_lo_at + !!out->cost_hi_at;
     const int nrhs = !!out->rhs_lo + !!out->rhs_hi + !!out->rhs_lo_at + !!out->rhs_hi_at;
     if (ncost % 4)
-        return bfail(b, LPG_ERR_ARG, "%s: out: %d of cost_lo, cost_hi, cost_lo_at, cost_hi_at given (all four or none)", call,
-                     ncost);
+        return fail(b, LPG_ERR_ARG, "%s: out: %d of cost_lo, cost_hi, cost_lo_at, cost_hi_at given (all four or none)", call,
+                    ncost);
     if (nrhs % 4)
-        return bfail(b, LPG_ERR_ARG, "%s: out: %d of rhs_lo, rhs_hi, rhs_lo_at, rhs_hi_at given (all four or none)", call, nrhs);
+        return fail(b, LPG_ERR_ARG, "%s: out: %d of rhs_lo, rhs_hi, rhs_lo_at, rhs_hi_at given (all four or none)", call, nrhs);
     if (!out->dual && !ncost && !nrhs)
-        return bfail(b, LPG_ERR_ARG, "%s: out: none of dual, cost_*, rhs_* given (nothing to compute)", call);
+        return fail(b, LPG_ERR_ARG, "%s: out: none of dual, cost_*, rhs_* given (nothing to compute)", call);
     if (!plain(b)) return wrong_kind(b, call);
     if (int rc = ident_ok(b, call, ident)) return rc;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     if (int rc = b->ragged ? raise_lds<k_batch_ranging<true>>(b, "k_batch_ranging", kRangingMaxLds)
                            : raise_lds<k_batch_ranging<false>>(b, "k_batch_ranging", kRangingMaxLds))
         return rc;
@@ -2276,7 +2252,7 @@ int lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *o
     DevBuf buf;
     if (hipMalloc(&buf.p, total * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
-        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(ident and the outputs of %lld LPs) failed", call, (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "%s: hipMalloc(ident and the outputs of %lld LPs) failed", call, (long long)b->count);
     }
     double *at = (double *)buf.p + nb;
     auto take = [&at](bool want, size_t n) { double *p = want ? at : nullptr; if (want) at += n; return p; };
@@ -2290,7 +2266,7 @@ int lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *o
     o.rhs_hi = take(nrhs, nb);
     o.rhs_lo_at = (int64_t *)take(nrhs, nb);
     o.rhs_hi_at = (int64_t *)take(nrhs, nb);
-    BHIPCHK(b, hipMemcpyAsync(buf.p, ident, nb * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(buf.p, ident, nb * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
     const size_t lds = ranging_lds(std::max(b->m, b->ncols));
     if (b->ragged)
         hipLaunchKernelGGL(k_batch_ranging<true>, dim3((unsigned)b->count), dim3(kBlock), lds, b->stream, bgeo(b),
@@ -2298,27 +2274,27 @@ int lpg_batch_ranging(lpg_batch *b, const int64_t *ident, const lpg_ranging_t *o
     else
         hipLaunchKernelGGL(k_batch_ranging<false>, dim3((unsigned)b->count), dim3(kBlock), lds, b->stream, bgeo(b),
                            (const int64_t *)buf.p, o);
-    BHIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipGetLastError());
     const struct { void *dst; const void *src; size_t n; } back[] = {
         {out->dual, o.dual, nb},           {out->cost_lo, o.cost_lo, nc},       {out->cost_hi, o.cost_hi, nc},
         {out->cost_lo_at, o.cost_lo_at, nc}, {out->cost_hi_at, o.cost_hi_at, nc}, {out->rhs_lo, o.rhs_lo, nb},
         {out->rhs_hi, o.rhs_hi, nb},       {out->rhs_lo_at, o.rhs_lo_at, nb},   {out->rhs_hi_at, o.rhs_hi_at, nb}};
     for (const auto &c : back)
-        if (c.dst) BHIPCHK(b, hipMemcpyAsync(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+        if (c.dst) LPG_HIPCHK(b, hipMemcpyAsync(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 
 int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64_t ld_mask, double int_tol, int rule,
                             lpg_branch_t *out) {
     const char *call = "lpg_batch_branch_select";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
-    if (!mask || !out) return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+    if (!mask || !out) return fail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : "out");
     if (!plain(b)) return wrong_kind(b, call);
     if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
-    if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
-    if (rule != LPG_BRANCH_MOST_FRACTIONAL && rule != LPG_BRANCH_FIRST) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
-    BHIPCHK(b, hipSetDevice(b->device));
+    if (!(int_tol >= 0.0 && int_tol < 0.5)) return fail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
+    if (rule != LPG_BRANCH_MOST_FRACTIONAL && rule != LPG_BRANCH_FIRST) return fail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     DevBuf dmask, dout;
     int64_t pitch;
     const hipError_t e = hipMalloc(&dout.p, (size_t)b->count * sizeof(BranchPick)) == hipSuccess
@@ -2326,43 +2302,43 @@ int lpg_batch_branch_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, in
                              : hipErrorOutOfMemory;
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
-        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and picks of %lld LPs) failed", call, (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and picks of %lld LPs) failed", call, (long long)b->count);
     }
-    BHIPCHK(b, e);
+    LPG_HIPCHK(b, e);
     if (rule == LPG_BRANCH_FIRST)
         hipLaunchKernelGGL(k_batch_branch_select<RULE_BLAND>, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
                            (const uint8_t *)dmask.p, nmask, pitch, int_tol, (BranchPick *)dout.p);
     else
         hipLaunchKernelGGL(k_batch_branch_select<RULE_DANTZIG>, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
                            (const uint8_t *)dmask.p, nmask, pitch, int_tol, (BranchPick *)dout.p);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipMemcpyAsync(out, dout.p, (size_t)b->count * sizeof(BranchPick), hipMemcpyDeviceToHost, b->stream));
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipMemcpyAsync(out, dout.p, (size_t)b->count * sizeof(BranchPick), hipMemcpyDeviceToHost, b->stream));
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 
 int lpg_batch_branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *row, const int8_t *dir) {
     const char *call = "lpg_batch_branch";
-    if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
+    if (!out) return fail(p, LPG_ERR_ARG, "%s: child is NULL", call);
     *out = nullptr;
     // what does not depend on the parent first
-    if (n < 1) return bfail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
-    if (!src || !row || !dir) return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !row ? "row" : "dir");
+    if (n < 1) return fail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
+    if (!src || !row || !dir) return fail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !row ? "row" : "dir");
     for (int64_t c = 0; c < n; c++)
         if (dir[c] != -1 && dir[c] != 1)
-            return bfail(p, LPG_ERR_ARG, "%s: dir[%lld] = %d (-1: x <= floor(v), +1: x >= ceil(v))", call, (long long)c,
-                         (int)dir[c]);
-    if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
+            return fail(p, LPG_ERR_ARG, "%s: dir[%lld] = %d (-1: x <= floor(v), +1: x >= ceil(v))", call, (long long)c,
+                        (int)dir[c]);
+    if (!p) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
     if (!plain(p)) return wrong_kind(p, call);
     for (int64_t c = 0; c < n; c++) {
         if (int rc = src_ok(p, call, c, src[c])) return rc;
         const int64_t m = lp_m(p, src[c]), ncols = lp_ncols(p, src[c]);
         if (row[c] < 0 || row[c] >= m)
-            return bfail(p, LPG_ERR_ARG, "%s: row[%lld] = %lld outside the rows 0..%lld of LP %lld", call, (long long)c,
-                         (long long)row[c], (long long)(m - 1), (long long)src[c]);
+            return fail(p, LPG_ERR_ARG, "%s: row[%lld] = %lld outside the rows 0..%lld of LP %lld", call, (long long)c,
+                        (long long)row[c], (long long)(m - 1), (long long)src[c]);
         if (m + 2 > LPG_BATCH_MAX_DIM || ncols + 1 > LPG_BATCH_MAX_DIM)
-            return bfail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + 2 = %lld, ncols + 1 = %lld exceed %d", call,
-                         (long long)c, (long long)src[c], (long long)(m + 2), (long long)(ncols + 1), LPG_BATCH_MAX_DIM);
+            return fail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + 2 = %lld, ncols + 1 = %lld exceed %d", call,
+                        (long long)c, (long long)src[c], (long long)(m + 2), (long long)(ncols + 1), LPG_BATCH_MAX_DIM);
     }
     lpg_batch *ch = nullptr;
     if (int rc = grow_create(&ch, p, call, n, src, std::vector<int64_t>((size_t)n, 1).data())) return rc;
@@ -2371,7 +2347,7 @@ int lpg_batch_branch(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *sr
     DevBuf djobs;
     if (hipMalloc(&djobs.p, jobs.size() * sizeof(BranchJob)) != hipSuccess) {
         (void)hipGetLastError();
-        bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs) failed", call, (long long)n);
+        fail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs) failed", call, (long long)n);
         return child_die(p, ch, LPG_ERR_OOM);
     }
     return grow_finish<k_batch_branch<false>, k_batch_branch<true>>(out, p, ch, call, hipSuccess, jobs, djobs, 0);
@@ -2382,14 +2358,14 @@ int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64
     const char *call = "lpg_batch_cut_select";
     // what does not depend on the batch first
     if (!mask || !ncut || !rows)
-        return bfail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : !ncut ? "ncut" : "rows");
+        return fail(b, LPG_ERR_ARG, "%s: %s is NULL", call, !mask ? "mask" : !ncut ? "ncut" : "rows");
     if (max_cuts < 1 || max_cuts > LPG_BATCH_MAX_CUTS)
-        return bfail(b, LPG_ERR_ARG, "%s: max_cuts = %lld outside 1..%d", call, (long long)max_cuts, LPG_BATCH_MAX_CUTS);
-    if (!(int_tol >= 0.0 && int_tol < 0.5)) return bfail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
+        return fail(b, LPG_ERR_ARG, "%s: max_cuts = %lld outside 1..%d", call, (long long)max_cuts, LPG_BATCH_MAX_CUTS);
+    if (!(int_tol >= 0.0 && int_tol < 0.5)) return fail(b, LPG_ERR_ARG, "%s: int_tol %g outside [0, 0.5)", call, int_tol);
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: batch is NULL", call);
     if (!plain(b)) return wrong_kind(b, call);
     if (int rc = mask_ok(b, call, nmask, ld_mask)) return rc;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     const size_t nbytes = (size_t)b->count * sizeof(int64_t), rbytes = nbytes * (size_t)max_cuts;
     DevBuf dmask, dncut, drows;
     int64_t pitch;
@@ -2398,34 +2374,34 @@ int lpg_batch_cut_select(lpg_batch *b, const uint8_t *mask, int64_t nmask, int64
                              : hipErrorOutOfMemory;
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
-        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and rows of %lld LPs) failed", call, (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "%s: hipMalloc(masks and rows of %lld LPs) failed", call, (long long)b->count);
     }
-    BHIPCHK(b, e);
+    LPG_HIPCHK(b, e);
     hipLaunchKernelGGL(k_batch_cut_select, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b),
                        (const uint8_t *)dmask.p, nmask, pitch, int_tol, max_cuts, (int64_t *)dncut.p, (int64_t *)drows.p);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipMemcpyAsync(ncut, dncut.p, nbytes, hipMemcpyDeviceToHost, b->stream));
-    BHIPCHK(b, hipMemcpyAsync(rows, drows.p, rbytes, hipMemcpyDeviceToHost, b->stream));
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipMemcpyAsync(ncut, dncut.p, nbytes, hipMemcpyDeviceToHost, b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(rows, drows.p, rbytes, hipMemcpyDeviceToHost, b->stream));
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 
 int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, const int64_t *first, const int64_t *rows,
                   const uint8_t *mask, int64_t nmask, int64_t ld_mask) {
     const char *call = "lpg_batch_cut";
-    if (!out) return bfail(p, LPG_ERR_ARG, "%s: child is NULL", call);
+    if (!out) return fail(p, LPG_ERR_ARG, "%s: child is NULL", call);
     *out = nullptr;
     // what does not depend on the parent first
-    if (n < 1) return bfail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
+    if (n < 1) return fail(p, LPG_ERR_ARG, "%s: n = %lld (need n >= 1)", call, (long long)n);
     if (!src || !first || !rows || !mask)
-        return bfail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !first ? "first" : !rows ? "rows" : "mask");
-    if (first[0] != 0) return bfail(p, LPG_ERR_ARG, "%s: first[0] = %lld (the offsets start at 0)", call, (long long)first[0]);
+        return fail(p, LPG_ERR_ARG, "%s: %s is NULL", call, !src ? "src" : !first ? "first" : !rows ? "rows" : "mask");
+    if (first[0] != 0) return fail(p, LPG_ERR_ARG, "%s: first[0] = %lld (the offsets start at 0)", call, (long long)first[0]);
     for (int64_t c = 0; c < n; c++)
         if (first[c + 1] <= first[c])
-            return bfail(p, LPG_ERR_ARG, "%s: first[%lld] = %lld is not above first[%lld] = %lld (every child has at least "
-                                         "one cut)", call, (long long)(c + 1), (long long)first[c + 1], (long long)c,
-                         (long long)first[c]);
-    if (!p) return bfail(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
+            return fail(p, LPG_ERR_ARG, "%s: first[%lld] = %lld is not above first[%lld] = %lld (every child has at least "
+                                        "one cut)", call, (long long)(c + 1), (long long)first[c + 1], (long long)c,
+                        (long long)first[c]);
+    if (!p) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "%s: parent is NULL", call);
     if (!plain(p)) return wrong_kind(p, call);
     if (int rc = mask_ok(p, call, nmask, ld_mask)) return rc;
     std::vector<int64_t> ks((size_t)n);
@@ -2434,23 +2410,23 @@ int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, 
         const int64_t k = ks[(size_t)c] = first[c + 1] - first[c];
         if (int rc = src_ok(p, call, c, src[c])) return rc;
         if (k > LPG_BATCH_MAX_CUTS)
-            return bfail(p, LPG_ERR_ARG, "%s: child %lld has %lld cuts, more than LPG_BATCH_MAX_CUTS = %d", call, (long long)c,
-                         (long long)k, LPG_BATCH_MAX_CUTS);
+            return fail(p, LPG_ERR_ARG, "%s: child %lld has %lld cuts, more than LPG_BATCH_MAX_CUTS = %d", call, (long long)c,
+                        (long long)k, LPG_BATCH_MAX_CUTS);
         const int64_t m = lp_m(p, src[c]), ncols = lp_ncols(p, src[c]);
         seen.assign((size_t)m, 0);
         for (int64_t t = first[c]; t < first[c + 1]; t++) {
             if (rows[t] < 0 || rows[t] >= m)
-                return bfail(p, LPG_ERR_ARG, "%s: rows[%lld] = %lld (child %lld) outside the rows 0..%lld of LP %lld", call,
-                             (long long)t, (long long)rows[t], (long long)c, (long long)(m - 1), (long long)src[c]);
+                return fail(p, LPG_ERR_ARG, "%s: rows[%lld] = %lld (child %lld) outside the rows 0..%lld of LP %lld", call,
+                            (long long)t, (long long)rows[t], (long long)c, (long long)(m - 1), (long long)src[c]);
             if (seen[(size_t)rows[t]])
-                return bfail(p, LPG_ERR_ARG, "%s: rows[%lld] = %lld appears twice in child %lld", call, (long long)t,
-                             (long long)rows[t], (long long)c);
+                return fail(p, LPG_ERR_ARG, "%s: rows[%lld] = %lld appears twice in child %lld", call, (long long)t,
+                            (long long)rows[t], (long long)c);
             seen[(size_t)rows[t]] = 1;
         }
         if (m + k + 1 > LPG_BATCH_MAX_DIM || ncols + k > LPG_BATCH_MAX_DIM)
-            return bfail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + %lld + 1 = %lld, ncols + %lld = %lld exceed %d", call,
-                         (long long)c, (long long)src[c], (long long)k, (long long)(m + k + 1), (long long)k,
-                         (long long)(ncols + k), LPG_BATCH_MAX_DIM);
+            return fail(p, LPG_ERR_ARG, "%s: child %lld of LP %lld: m + %lld + 1 = %lld, ncols + %lld = %lld exceed %d", call,
+                        (long long)c, (long long)src[c], (long long)k, (long long)(m + k + 1), (long long)k,
+                        (long long)(ncols + k), LPG_BATCH_MAX_DIM);
     }
     lpg_batch *ch = nullptr;
     if (int rc = grow_create(&ch, p, call, n, src, ks.data())) return rc;
@@ -2466,7 +2442,7 @@ int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, 
                        : hipErrorOutOfMemory;
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
-        bfail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, %lld rows, masks) failed", call, (long long)n, (long long)first[n]);
+        fail(ch, LPG_ERR_OOM, "%s: hipMalloc(%lld jobs, %lld rows, masks) failed", call, (long long)n, (long long)first[n]);
         return child_die(p, ch, LPG_ERR_OOM);
     }
     if (e == hipSuccess)
@@ -2475,7 +2451,7 @@ int lpg_batch_cut(lpg_batch **out, lpg_batch *p, int64_t n, const int64_t *src, 
                                                               (const uint8_t *)dmask.p, nmask, pitch);
 }
 
-const char *lpg_batch_last_error(const lpg_batch *b) { return b ? b->err : g_berr; }
+const char *lpg_batch_last_error(const lpg_batch *b) { return b ? b->err : thread_err<lpg_batch>(); }
 
 int lpg_batch_create(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, uint32_t flags) {
     return batch_create(out, device, count, m, ncols, flags, 1, "lpg_batch_create");
@@ -2486,58 +2462,58 @@ int lpg_batch_create_big_m(lpg_batch **out, int device, int64_t count, int64_t m
 }
 
 int lpg_batch_create_goal(lpg_batch **out, int device, int64_t count, int64_t m, int64_t ncols, int nlevels, uint32_t flags) {
-    if (!out) return bfail(nullptr, LPG_ERR_ARG, "out is NULL");
+    if (!out) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (nlevels < 1 || nlevels > LPG_GOAL_MAX_LEVELS)
-        return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_create_goal: nlevels = %d outside 1..%d (LPG_GOAL_MAX_LEVELS)", nlevels,
-                     LPG_GOAL_MAX_LEVELS);
+        return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "lpg_batch_create_goal: nlevels = %d outside 1..%d (LPG_GOAL_MAX_LEVELS)",
+                               nlevels, LPG_GOAL_MAX_LEVELS);
     return batch_create(out, device, count, m, ncols, flags, nlevels, "lpg_batch_create_goal", true);
 }
 
 int lpg_batch_solve_goal(lpg_batch *b, const double *cost, int64_t ld_lp, int64_t ld_level, int64_t max_pivots, int rule,
                          lpg_result *res, double *attain) {
     const char *call = "lpg_batch_solve_goal";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (!b->goal) {
         if (b->nobj == 2) return wrong_kind(b, call);
-        return bfail(b, LPG_ERR_STATE, "%s: the batch has one objective row (lpg_batch_create); a goal programme needs a "
-                                       "batch from lpg_batch_create_goal; nothing has pivoted", call);
+        return fail(b, LPG_ERR_STATE, "%s: the batch has one objective row (lpg_batch_create); a goal programme needs a "
+                                      "batch from lpg_batch_create_goal; nothing has pivoted", call);
     }
     const int64_t N = b->ncols - 1, K = b->nobj;
-    if (!cost) return bfail(b, LPG_ERR_ARG, "%s: cost is NULL (a goal batch keeps no costs of its own)", call);
-    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
-    if (ld_level < N) return bfail(b, LPG_ERR_ARG, "%s: ld_level %lld < N = %lld", call, (long long)ld_level, (long long)N);
+    if (!cost) return fail(b, LPG_ERR_ARG, "%s: cost is NULL (a goal batch keeps no costs of its own)", call);
+    if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return fail(b, LPG_ERR_ARG, "%s: rule %d", call, rule);
+    if (ld_level < N) return fail(b, LPG_ERR_ARG, "%s: ld_level %lld < N = %lld", call, (long long)ld_level, (long long)N);
     if (ld_lp / K < ld_level)
-        return bfail(b, LPG_ERR_ARG, "%s: ld_lp %lld < nlevels * ld_level = %lld x %lld", call, (long long)ld_lp, (long long)K,
-                     (long long)ld_level);
-    if (max_pivots < 0) return bfail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
-    BHIPCHK(b, hipSetDevice(b->device));
+        return fail(b, LPG_ERR_ARG, "%s: ld_lp %lld < nlevels * ld_level = %lld x %lld", call, (long long)ld_lp, (long long)K,
+                    (long long)ld_level);
+    if (max_pivots < 0) return fail(b, LPG_ERR_ARG, "%s: max_pivots < 0", call);
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     // the costs packed (the caller's padding is never read), and the attained levels beside them
     const size_t total = (size_t)b->count * (size_t)K * (size_t)N;
     if (!b->cost && hipMalloc(&b->cost, total * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         b->cost = nullptr;
-        return bfail(b, LPG_ERR_OOM, "hipMalloc(%d levels of costs of %lld LPs) failed", b->nobj, (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "hipMalloc(%d levels of costs of %lld LPs) failed", b->nobj, (long long)b->count);
     }
     if (!b->attain && hipMalloc(&b->attain, (size_t)b->count * (size_t)K * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         b->attain = nullptr;
-        return bfail(b, LPG_ERR_OOM, "hipMalloc(%d attained levels of %lld LPs) failed", b->nobj, (long long)b->count);
+        return fail(b, LPG_ERR_OOM, "hipMalloc(%d attained levels of %lld LPs) failed", b->nobj, (long long)b->count);
     }
     if (ld_level == N && ld_lp == K * N) {                        // no padding: the caller's array is the packed one
-        BHIPCHK(b, hipMemcpy(b->cost, cost, total * sizeof(double), hipMemcpyHostToDevice));
+        LPG_HIPCHK(b, hipMemcpy(b->cost, cost, total * sizeof(double), hipMemcpyHostToDevice));
     } else {
         double *packed = (double *)malloc(total * sizeof(double));
-        if (!packed) return bfail(b, LPG_ERR_OOM, "%s: malloc(%zu bytes to pack the costs) failed", call, total * sizeof(double));
+        if (!packed) return fail(b, LPG_ERR_OOM, "%s: malloc(%zu bytes to pack the costs) failed", call, total * sizeof(double));
         for (int64_t q = 0; q < b->count; q++)
             for (int64_t k = 0; k < K; k++)
                 memcpy(packed + (size_t)((q * K + k) * N), cost + q * ld_lp + k * ld_level, (size_t)N * sizeof(double));
         const hipError_t e = hipMemcpy(b->cost, packed, total * sizeof(double), hipMemcpyHostToDevice);
         free(packed);
-        BHIPCHK(b, e);
+        LPG_HIPCHK(b, e);
     }
     if (int rc = batch_run(b, max_pivots, M_GOAL, rule, res)) return rc;
-    if (attain) BHIPCHK(b, hipMemcpy(attain, b->attain, (size_t)b->count * (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
+    if (attain) LPG_HIPCHK(b, hipMemcpy(attain, b->attain, (size_t)b->count * (size_t)K * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2563,7 +2539,7 @@ void lpg_batch_destroy(lpg_batch *b) {
 }
 
 int lpg_batch_info(const lpg_batch *b, lpg_batch_info_t *o) {
-    if (!b || !o) return bfail(const_cast<lpg_batch *>(b), LPG_ERR_ARG, "NULL argument");
+    if (!b || !o) return fail(const_cast<lpg_batch *>(b), LPG_ERR_ARG, "NULL argument");
     o->count = b->count;
     o->m = b->m;
     o->ncols = b->ncols;
@@ -2584,16 +2560,16 @@ int lpg_batch_create_ragged(lpg_batch **out, int device, int64_t count, const in
 
 int lpg_batch_shape(const lpg_batch *cb, int64_t lp, lpg_batch_shape_t *o) {
     lpg_batch *b = const_cast<lpg_batch *>(cb);
-    if (!b || !o) return bfail(b, LPG_ERR_ARG, "lpg_batch_shape: NULL argument");
+    if (!b || !o) return fail(b, LPG_ERR_ARG, "lpg_batch_shape: NULL argument");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_shape", "lpg_batch_info");
     if (lp < 0 || lp >= b->count)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_shape: LP %lld outside the batch of %lld", (long long)lp, (long long)b->count);
+        return fail(b, LPG_ERR_ARG, "lpg_batch_shape: LP %lld outside the batch of %lld", (long long)lp, (long long)b->count);
     *o = b->pub[(size_t)lp];
     return 0;
 }
 
 int lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, const int64_t *basis) {
-    if (!b || !tableaus) return bfail(b, LPG_ERR_ARG, "lpg_batch_load_packed: NULL argument");
+    if (!b || !tableaus) return fail(b, LPG_ERR_ARG, "lpg_batch_load_packed: NULL argument");
     if (b->goal) return wrong_kind(b, "lpg_batch_load_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_load_packed", "lpg_batch_load");
     if (int rc = range_ok(b, "lpg_batch_load_packed", first, n)) return rc;
@@ -2605,11 +2581,11 @@ int lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *
             for (int64_t i = 0; i < s.m; i++) {
                 const int64_t k = basis[s.b_off - s0.b_off + i];
                 if (k < 1 || k >= s.ncols)
-                    return bfail(b, LPG_ERR_ARG, "lpg_batch_load_packed: basis[%lld] of LP %lld out of range 1..%lld",
-                                 (long long)i, (long long)q, (long long)(s.ncols - 1));
+                    return fail(b, LPG_ERR_ARG, "lpg_batch_load_packed: basis[%lld] of LP %lld out of range 1..%lld",
+                                (long long)i, (long long)q, (long long)(s.ncols - 1));
             }
         }
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     // the LPs' device images are back to back: build them on the host (rows at
     // pitch ld, zero padding) and move them in one copy
     const int64_t doubles = s1.t_off + (int64_t)(s1.m + b->nobj) * s1.ld - s0.t_off;
@@ -2620,28 +2596,28 @@ int lpg_batch_load_packed(lpg_batch *b, int64_t first, int64_t n, const double *
         double *dst = img.data() + (s.t_off - s0.t_off);
         for (int64_t i = 0; i < s.m + b->nobj; i++, src += s.ncols, dst += s.ld) memcpy(dst, src, (size_t)s.ncols * sizeof(double));
     }
-    BHIPCHK(b, hipMemcpyAsync(b->T + s0.t_off, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(b->T + s0.t_off, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
     if (basis)
-        BHIPCHK(b, hipMemcpyAsync(b->basis + s0.b_off, basis, (size_t)(s1.b_off + s1.m - s0.b_off) * sizeof(int64_t),
+        LPG_HIPCHK(b, hipMemcpyAsync(b->basis + s0.b_off, basis, (size_t)(s1.b_off + s1.m - s0.b_off) * sizeof(int64_t),
                                   hipMemcpyHostToDevice, b->stream));
     hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(n)), dim3(kBlock), 0, b->stream, b->lp, first, n);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     if (first == 0 && n == b->count) b->pivoted = false;
     return 0;
 }
 
 int lpg_batch_get_rows_packed(lpg_batch *b, int64_t first, int64_t n, double *out) {
-    if (!b || !out) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows_packed: NULL argument");
+    if (!b || !out) return fail(b, LPG_ERR_ARG, "lpg_batch_get_rows_packed: NULL argument");
     if (b->goal) return wrong_kind(b, "lpg_batch_get_rows_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_get_rows_packed", "lpg_batch_get_rows");
     if (int rc = range_ok(b, "lpg_batch_get_rows_packed", first, n)) return rc;
     if (n == 0) return 0;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     const BatchShape &s0 = b->shape[(size_t)first], &s1 = b->shape[(size_t)(first + n - 1)];
     std::vector<double> img((size_t)(s1.t_off + (int64_t)(s1.m + b->nobj) * s1.ld - s0.t_off));
-    BHIPCHK(b, hipMemcpyAsync(img.data(), b->T + s0.t_off, img.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(img.data(), b->T + s0.t_off, img.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     for (int64_t q = first; q < first + n; q++) {
         const BatchShape &s = b->shape[(size_t)q];
         const double *src = img.data() + (s.t_off - s0.t_off);
@@ -2651,27 +2627,27 @@ int lpg_batch_get_rows_packed(lpg_batch *b, int64_t first, int64_t n, double *ou
 }
 
 int lpg_batch_get_basis_packed(lpg_batch *b, int64_t first, int64_t n, int64_t *basis) {
-    if (!b || !basis) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_basis_packed: NULL argument");
+    if (!b || !basis) return fail(b, LPG_ERR_ARG, "lpg_batch_get_basis_packed: NULL argument");
     if (b->goal) return wrong_kind(b, "lpg_batch_get_basis_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_get_basis_packed", "lpg_batch_get_basis");
     if (int rc = range_ok(b, "lpg_batch_get_basis_packed", first, n)) return rc;
     if (n == 0) return 0;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     const BatchShape &s0 = b->shape[(size_t)first], &s1 = b->shape[(size_t)(first + n - 1)];
-    BHIPCHK(b, hipMemcpy(basis, b->basis + s0.b_off, (size_t)(s1.b_off + s1.m - s0.b_off) * sizeof(int64_t),
+    LPG_HIPCHK(b, hipMemcpy(basis, b->basis + s0.b_off, (size_t)(s1.b_off + s1.m - s0.b_off) * sizeof(int64_t),
                          hipMemcpyDeviceToHost));
     return 0;
 }
 
 int lpg_batch_set_objective_packed(lpg_batch *b, const double *cost) {
-    if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective_packed: NULL argument");
+    if (!b || !cost) return fail(b, LPG_ERR_ARG, "lpg_batch_set_objective_packed: NULL argument");
     if (!plain(b)) return wrong_kind(b, "lpg_batch_set_objective_packed");
     if (!b->ragged) return wrong_layout(b, "lpg_batch_set_objective_packed", "lpg_batch_set_objective");
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     if (int rc = stage_costs(b, cost, 0)) return rc;
     hipLaunchKernelGGL(k_batch_set_objective, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b), b->cost);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 
@@ -2686,46 +2662,46 @@ int lpg_batch_solve_big_m_ragged(lpg_batch *b, const int64_t *art_first, const d
 }
 
 int lpg_batch_load(lpg_batch *b, int64_t first, int64_t n, const double *tableaus, int64_t ld, const int64_t *basis) {
-    if (!b || !tableaus) return bfail(b, LPG_ERR_ARG, "lpg_batch_load: NULL argument");
+    if (!b || !tableaus) return fail(b, LPG_ERR_ARG, "lpg_batch_load: NULL argument");
     if (b->ragged) return wrong_layout(b, "lpg_batch_load", "lpg_batch_load_packed");
     if (int rc = range_ok(b, "lpg_batch_load", first, n)) return rc;
-    if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_load: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
+    if (ld < b->ncols) return fail(b, LPG_ERR_ARG, "lpg_batch_load: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
     if (basis)
         for (int64_t q = 0; q < n * b->m; q++)
             if (basis[q] < 1 || basis[q] >= b->ncols)
-                return bfail(b, LPG_ERR_ARG, "lpg_batch_load: basis[%lld] of LP %lld out of range 1..%lld",
-                             (long long)(q % b->m), (long long)(first + q / b->m), (long long)(b->ncols - 1));
+                return fail(b, LPG_ERR_ARG, "lpg_batch_load: basis[%lld] of LP %lld out of range 1..%lld",
+                            (long long)(q % b->m), (long long)(first + q / b->m), (long long)(b->ncols - 1));
     if (n == 0) return 0;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     const int64_t rows = b->m + b->nobj;
     // rows are back to back on both sides: one strided copy of n * (m + nobj) rows
-    BHIPCHK(b, hipMemcpy2DAsync(b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double), tableaus,
+    LPG_HIPCHK(b, hipMemcpy2DAsync(b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double), tableaus,
                                 (size_t)ld * sizeof(double), (size_t)b->ncols * sizeof(double), (size_t)(n * rows),
                                 hipMemcpyHostToDevice, b->stream));
     if (basis)
-        BHIPCHK(b, hipMemcpyAsync(b->basis + first * b->m, basis, (size_t)(n * b->m) * sizeof(int64_t),
+        LPG_HIPCHK(b, hipMemcpyAsync(b->basis + first * b->m, basis, (size_t)(n * b->m) * sizeof(int64_t),
                                   hipMemcpyHostToDevice, b->stream));
     hipLaunchKernelGGL(k_batch_reset, dim3(blocks_for(n)), dim3(kBlock), 0, b->stream, b->lp, first, n);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     if (first == 0 && n == b->count) b->pivoted = false;
     return 0;
 }
 
 int lpg_batch_generate(lpg_batch *b, int64_t n, uint64_t seed, int kind) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (!plain(b)) return wrong_kind(b, "lpg_batch_generate");
     if (b->ragged) return wrong_layout(b, "lpg_batch_generate", "lpg_batch_load_packed (a ragged batch has no generator)");
     if (n < 1 || b->ncols != n + b->m + 1)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
-                     (long long)(n + b->m + 1));
+        return fail(b, LPG_ERR_ARG, "lpg_batch_generate: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
+                    (long long)(n + b->m + 1));
     if (kind != LPG_GEN_DENSE && kind != LPG_GEN_DEGENERATE && kind != LPG_GEN_DUAL)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_generate: kind %d (dense, degenerate or dual only)", kind);
+        return fail(b, LPG_ERR_ARG, "lpg_batch_generate: kind %d (dense, degenerate or dual only)", kind);
     return generate(b, n, seed, kind);
 }
 
 int lpg_batch_set_tolerances(lpg_batch *b, double eps_piv, double eps_opt) {
-    if (!b || !(eps_piv >= 0) || !(eps_opt >= 0)) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_tolerances: bad tolerances");
+    if (!b || !(eps_piv >= 0) || !(eps_opt >= 0)) return fail(b, LPG_ERR_ARG, "lpg_batch_set_tolerances: bad tolerances");
     b->eps_piv = eps_piv;
     b->eps_opt = eps_opt;
     return 0;
@@ -2736,24 +2712,24 @@ int lpg_batch_set_active_columns(lpg_batch *b, int64_t nact) {
     if (b && b->ragged)
         return wrong_layout(b, "lpg_batch_set_active_columns", "lpg_batch_solve_two_phase_ragged, which sets them per LP");
     if (!b || nact < 1 || nact > b->ncols - 1)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_set_active_columns: nact out of range 1..N");
+        return fail(b, LPG_ERR_ARG, "lpg_batch_set_active_columns: nact out of range 1..N");
     b->nact = nact;
     return 0;
 }
 
 int lpg_batch_reserve_log(lpg_batch *b, int64_t npivots) {
-    if (!b || npivots < 0) return bfail(b, LPG_ERR_ARG, "lpg_batch_reserve_log: bad arguments");
-    if (b->pivoted) return bfail(b, LPG_ERR_STATE, "lpg_batch_reserve_log: set the log capacity before the first solve");
+    if (!b || npivots < 0) return fail(b, LPG_ERR_ARG, "lpg_batch_reserve_log: bad arguments");
+    if (b->pivoted) return fail(b, LPG_ERR_STATE, "lpg_batch_reserve_log: set the log capacity before the first solve");
     if (npivots > (int64_t)0x7fffffff || (double)npivots * (double)b->count > 4e9)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_reserve_log: %lld pivots x %lld LPs is too large", (long long)npivots,
-                     (long long)b->count);
-    BHIPCHK(b, hipSetDevice(b->device));
+        return fail(b, LPG_ERR_ARG, "lpg_batch_reserve_log: %lld pivots x %lld LPs is too large", (long long)npivots,
+                    (long long)b->count);
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     return alloc_log(b, npivots);
 }
 
 int lpg_batch_solve(lpg_batch *b, int64_t max_pivots, int rule, lpg_result *out) {
     if (b && !plain(b)) return wrong_kind(b, "lpg_batch_solve");
-    if (b && rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return bfail(b, LPG_ERR_ARG, "lpg_batch_solve: rule %d", rule);
+    if (b && rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND) return fail(b, LPG_ERR_ARG, "lpg_batch_solve: rule %d", rule);
     return batch_run(b, max_pivots, M_PRIMAL, rule, out);
 }
 
@@ -2773,65 +2749,65 @@ int lpg_batch_solve_big_m(lpg_batch *b, int64_t art_first, const double *cost, i
 }
 
 int lpg_batch_set_objective(lpg_batch *b, const double *cost, int64_t ld_cost) {
-    if (!b || !cost) return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: NULL argument");
+    if (!b || !cost) return fail(b, LPG_ERR_ARG, "lpg_batch_set_objective: NULL argument");
     if (!plain(b)) return wrong_kind(b, "lpg_batch_set_objective");
     if (b->ragged) return wrong_layout(b, "lpg_batch_set_objective", "lpg_batch_set_objective_packed");
     if (ld_cost < b->ncols - 1)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_set_objective: ld_cost %lld < N = %lld", (long long)ld_cost,
-                     (long long)(b->ncols - 1));
-    BHIPCHK(b, hipSetDevice(b->device));
+        return fail(b, LPG_ERR_ARG, "lpg_batch_set_objective: ld_cost %lld < N = %lld", (long long)ld_cost,
+                    (long long)(b->ncols - 1));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     if (int rc = stage_costs(b, cost, ld_cost)) return rc;
     hipLaunchKernelGGL(k_batch_set_objective, dim3((unsigned)b->count), dim3(kBlock), 0, b->stream, bgeo(b), b->cost);
-    BHIPCHK(b, hipGetLastError());
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 
 int lpg_batch_generate_artificial(lpg_batch *b, int64_t n, uint64_t seed, int64_t *art_first) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (b->goal) return wrong_kind(b, "lpg_batch_generate_artificial");
     if (b->ragged)
         return wrong_layout(b, "lpg_batch_generate_artificial", "lpg_batch_load_packed (a ragged batch has no generator)");
     if (n < 1 || b->ncols != n + b->m + 1)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_generate_artificial: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
-                     (long long)(n + b->m + 1));
+        return fail(b, LPG_ERR_ARG, "lpg_batch_generate_artificial: ncols %lld != n + m + 1 = %lld", (long long)b->ncols,
+                    (long long)(n + b->m + 1));
     if (int rc = generate(b, n, seed, (int)LPG_GEN_ARTIFICIAL)) return rc;
     if (art_first) *art_first = 1 + n + (b->m + 1) / 2;
     return 0;
 }
 
 int lpg_batch_get_rows(lpg_batch *b, int64_t first, int64_t n, double *out, int64_t ld) {
-    if (!b || !out) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: NULL argument");
+    if (!b || !out) return fail(b, LPG_ERR_ARG, "lpg_batch_get_rows: NULL argument");
     if (b->ragged) return wrong_layout(b, "lpg_batch_get_rows", "lpg_batch_get_rows_packed");
     if (int rc = range_ok(b, "lpg_batch_get_rows", first, n)) return rc;
-    if (ld < b->ncols) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_rows: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
+    if (ld < b->ncols) return fail(b, LPG_ERR_ARG, "lpg_batch_get_rows: ld %lld < ncols %lld", (long long)ld, (long long)b->ncols);
     if (n == 0) return 0;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     const int64_t rows = b->m + b->nobj;
-    BHIPCHK(b, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double),
+    LPG_HIPCHK(b, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), b->T + first * rows * b->ld, (size_t)b->ld * sizeof(double),
                                 (size_t)b->ncols * sizeof(double), (size_t)(n * rows), hipMemcpyDeviceToHost, b->stream));
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     return 0;
 }
 
 int lpg_batch_get_basis(lpg_batch *b, int64_t first, int64_t n, int64_t *basis) {
-    if (!b || !basis) return bfail(b, LPG_ERR_ARG, "lpg_batch_get_basis: NULL argument");
+    if (!b || !basis) return fail(b, LPG_ERR_ARG, "lpg_batch_get_basis: NULL argument");
     if (b->ragged) return wrong_layout(b, "lpg_batch_get_basis", "lpg_batch_get_basis_packed");
     if (int rc = range_ok(b, "lpg_batch_get_basis", first, n)) return rc;
     if (n == 0) return 0;
-    BHIPCHK(b, hipSetDevice(b->device));
-    BHIPCHK(b, hipMemcpy(basis, b->basis + first * b->m, (size_t)(n * b->m) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipMemcpy(basis, b->basis + first * b->m, (size_t)(n * b->m) * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int64_t max) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "batch is NULL");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "batch is NULL");
     if (lp < 0 || lp >= b->count)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_get_log: LP %lld outside the batch of %lld", (long long)lp, (long long)b->count);
+        return fail(b, LPG_ERR_ARG, "lpg_batch_get_log: LP %lld outside the batch of %lld", (long long)lp, (long long)b->count);
     if (!b->logk) return 0;
-    BHIPCHK(b, hipSetDevice(b->device));
+    LPG_HIPCHK(b, hipSetDevice(b->device));
     BatchLP h;
-    BHIPCHK(b, hipMemcpy(&h, b->lp + lp, sizeof h, hipMemcpyDeviceToHost));
+    LPG_HIPCHK(b, hipMemcpy(&h, b->lp + lp, sizeof h, hipMemcpyDeviceToHost));
     const int64_t rec = std::min(h.pivots, b->logcap);
     const int64_t n = std::max<int64_t>(0, std::min(rec, max));
     if (n > 0 && (k || r)) {
@@ -2839,7 +2815,7 @@ int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int6
         for (int w = 0; w < 2; w++) {
             int64_t *dst = w ? r : k;
             if (!dst) continue;
-            BHIPCHK(b, hipMemcpy(t.data(), (w ? b->logr : b->logk) + lp * b->logcap, (size_t)n * sizeof(int32_t),
+            LPG_HIPCHK(b, hipMemcpy(t.data(), (w ? b->logr : b->logk) + lp * b->logcap, (size_t)n * sizeof(int32_t),
                                  hipMemcpyDeviceToHost));
             for (int64_t q = 0; q < n; q++) dst[q] = t[(size_t)q];
         }
@@ -2849,10 +2825,10 @@ int64_t lpg_batch_get_log(lpg_batch *b, int64_t lp, int64_t *k, int64_t *r, int6
 
 int lpg_batch_active_columns(const lpg_batch *cb, int64_t lp, int64_t *nact, int64_t *art_first) {
     lpg_batch *b = const_cast<lpg_batch *>(cb);
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "lpg_batch_active_columns: batch is NULL");
+    if (!b) return fail<lpg_batch>(nullptr, LPG_ERR_ARG, "lpg_batch_active_columns: batch is NULL");
     if (lp < 0 || lp >= b->count)
-        return bfail(b, LPG_ERR_ARG, "lpg_batch_active_columns: LP %lld outside the batch of %lld", (long long)lp,
-                     (long long)b->count);
+        return fail(b, LPG_ERR_ARG, "lpg_batch_active_columns: LP %lld outside the batch of %lld", (long long)lp,
+                    (long long)b->count);
     if (nact) *nact = lp_nact(b, lp);
     if (art_first) *art_first = b->ragged ? b->shape[(size_t)lp].art_first : b->ncols;
     return 0;

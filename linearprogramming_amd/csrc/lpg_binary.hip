@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,6 +30,7 @@
 #include "../../include/lpg.h"
 #include "lpg_internal.h"
 #include "lpg_device.h"
+#include "lpg_host.h"
 
 namespace lpg {
 
@@ -317,60 +317,21 @@ __global__ __launch_bounds__(kBlock) void k_binary_solve(BinaryGeo g) {
 
 using namespace lpg;
 
-struct lpg_binary {
-    int device = 0;
-    int64_t count = 0, m = 0, n = 0, nsub = 0;
+struct lpg_binary : BatchHost {
+    int64_t m = 0, n = 0, nsub = 0;
     int split = 0;
     uint32_t flags = 0;
     int tier = LPG_BATCH_TIER_LDS, rpl = 1, chunk = LPG_BINARY_DEFAULT_CHUNK;
-    int64_t lds = 0;
-    bool on_device = false;       // the device side exists (made by the first call that needs it)
-    bool loaded = false;          // every problem has data
-    std::vector<uint8_t> have;    // per problem: loaded
     bool fresh = true;            // the searches stand before their roots' init
     bool any_running = true;
-    bool solved = false;
-    bool lds_raised = false;
     double *At = nullptr, *L = nullptr, *U = nullptr, *c = nullptr, *rows = nullptr;
     BinSub *sub = nullptr;
     int32_t *running = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int64_t launches = 0;
-    double kernel_ms = 0.0;
     std::vector<lpg_binary_result> res;      // of the last solve, reduced over the sub-searches
     std::vector<int8_t> x;
-    char err[512] = {0};
 };
 
 namespace {
-
-thread_local char g_berr[512];
-
-int bfail(lpg_binary *b, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (b) snprintf(b->err, sizeof b->err, "%s", buf);
-    snprintf(g_berr, sizeof g_berr, "%s", buf);
-    return code;
-}
-
-#define NHIPCHK(b, x)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            (void)hipGetLastError();                                                  \
-            return bfail((b), LPG_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));   \
-        }                                                                             \
-    } while (0)
-
-bool env_is(const char *name, const char *value) {
-    const char *e = getenv(name);
-    return e && !strcmp(e, value);
-}
 
 const void *solve_kernel(int rpl, int tier) {
     if (tier == LPG_BATCH_TIER_LDS)
@@ -380,65 +341,6 @@ const void *solve_kernel(int rpl, int tier) {
     return rpl == 1   ? (const void *)k_binary_solve<1, LPG_BATCH_TIER_GLOBAL>
            : rpl == 2 ? (const void *)k_binary_solve<2, LPG_BATCH_TIER_GLOBAL>
                       : (const void *)k_binary_solve<4, LPG_BATCH_TIER_GLOBAL>;
-}
-
-void release_device(lpg_binary *b) {
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (void *p : {(void *)b->At, (void *)b->L, (void *)b->U, (void *)b->c, (void *)b->rows, (void *)b->sub,
-                    (void *)b->running})
-        if (p) (void)hipFree(p);
-    b->At = b->L = b->U = b->c = b->rows = nullptr;
-    b->sub = nullptr;
-    b->running = nullptr;
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    b->ev0 = b->ev1 = nullptr;
-    b->stream = nullptr;
-    b->on_device = false;
-}
-
-// Device memory, stream, events: made by the first call that moves data or
-// launches, so that every refusal is answered before the library touches a
-// device. A setup that fails is taken down again.
-int ensure_device(lpg_binary *b, const char *call) {
-    hipError_t e = hipSetDevice(b->device);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return bfail(b, LPG_ERR_DEVICE, "%s: hipSetDevice(%d): %s", call, b->device, hipGetErrorString(e));
-    }
-    if (b->on_device) return 0;
-    const size_t ab = (size_t)(b->count * b->n * b->m) * sizeof(double);
-    const size_t rb = (size_t)(b->count * b->m) * sizeof(double);
-    if (hipMalloc(&b->At, ab) != hipSuccess || hipMalloc(&b->L, rb) != hipSuccess || hipMalloc(&b->U, rb) != hipSuccess ||
-        hipMalloc(&b->c, (size_t)(b->count * b->n) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&b->rows, (size_t)(b->nsub * 3 * b->m) * sizeof(double)) != hipSuccess ||
-        hipMalloc(&b->sub, (size_t)b->nsub * sizeof(BinSub)) != hipSuccess ||
-        hipMalloc(&b->running, sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        release_device(b);
-        return bfail(b, LPG_ERR_OOM, "%s: hipMalloc(batch of %lld problems, %lld sub-searches) failed", call,
-                     (long long)b->count, (long long)b->nsub);
-    }
-    if ((e = hipStreamCreate(&b->stream)) != hipSuccess || (e = hipEventCreate(&b->ev0)) != hipSuccess ||
-        (e = hipEventCreate(&b->ev1)) != hipSuccess) {
-        (void)hipGetLastError();
-        release_device(b);
-        return bfail(b, LPG_ERR_DEVICE, "%s: stream and events: %s", call, hipGetErrorString(e));
-    }
-    b->on_device = true;
-    return 0;
-}
-
-int raise_lds(lpg_binary *b, const char *call) {
-    if (b->lds_raised) return 0;
-    if (hipFuncSetAttribute(solve_kernel(b->rpl, b->tier), hipFuncAttributeMaxDynamicSharedMemorySize, kBinaryMaxLds) !=
-        hipSuccess) {
-        (void)hipGetLastError();
-        return bfail(b, LPG_ERR_DEVICE, "%s: hipFuncSetAttribute(%d bytes of LDS) failed", call, kBinaryMaxLds);
-    }
-    b->lds_raised = true;
-    return 0;
 }
 
 BinaryGeo geo_of(const lpg_binary *b) {
@@ -479,34 +381,35 @@ const char *what_is(double v) { return v != v ? "NaN" : (v == INFINITY || v == -
 
 extern "C" {
 
-const char *lpg_binary_last_error(const lpg_binary *b) { return b ? b->err : g_berr; }
+const char *lpg_binary_last_error(const lpg_binary *b) { return b ? b->err : thread_err<lpg_binary>(); }
 
 int lpg_binary_create(lpg_binary **out, int device, int64_t count, int64_t m, int64_t n, int32_t split, uint32_t flags) {
     const char *call = "lpg_binary_create";
-    if (!out) return bfail(nullptr, LPG_ERR_ARG, "%s: out is NULL", call);
+    lpg_binary *b = nullptr;           // not made yet: the refusals below go to the thread's buffer only
+    if (!out) return fail(b, LPG_ERR_ARG, "%s: out is NULL", call);
     *out = nullptr;
     if (count < 1 || m < 1 || m > LPG_BINARY_MAX_M || n < 1 || n > LPG_BINARY_MAX_N)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: bad shape count=%lld m=%lld n=%lld (need count >= 1, 1 <= m <= %d, "
-                                           "1 <= n <= %d)", call, (long long)count, (long long)m, (long long)n,
-                     LPG_BINARY_MAX_M, LPG_BINARY_MAX_N);
+        return fail(b, LPG_ERR_ARG, "%s: bad shape count=%lld m=%lld n=%lld (need count >= 1, 1 <= m <= %d, "
+                                    "1 <= n <= %d)", call, (long long)count, (long long)m, (long long)n,
+                    LPG_BINARY_MAX_M, LPG_BINARY_MAX_N);
     const int64_t smax = n < LPG_BINARY_MAX_SPLIT ? n : LPG_BINARY_MAX_SPLIT;
     if (split < 0 || split > smax)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: split %d outside 0..min(n, %d) = %lld", call, split, LPG_BINARY_MAX_SPLIT,
-                     (long long)smax);
+        return fail(b, LPG_ERR_ARG, "%s: split %d outside 0..min(n, %d) = %lld", call, split, LPG_BINARY_MAX_SPLIT,
+                    (long long)smax);
     if (flags & ~(uint32_t)LPG_BINARY_MAXIMIZE)
-        return bfail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_BINARY_MAXIMIZE only)", call, flags);
-    if (device < 0) return bfail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+        return fail(b, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_BINARY_MAXIMIZE only)", call, flags);
+    if (device < 0) return fail(b, LPG_ERR_ARG, "%s: device %d", call, device);
     if (count > ((int64_t)0x7fffffff >> split))
-        return bfail(nullptr, LPG_ERR_ARG, "%s: count * 2^split = %lld x %d exceeds 2^31 - 1", call, (long long)count,
-                     1 << split);
+        return fail(b, LPG_ERR_ARG, "%s: count * 2^split = %lld x %d exceeds 2^31 - 1", call, (long long)count,
+                    1 << split);
     int chunk = LPG_BINARY_DEFAULT_CHUNK;
     if (const char *ce = getenv("LPG_BINARY_CHUNK")) {
         const long long v = atoll(ce);
         if (v < 1 || v > (1 << 24))
-            return bfail(nullptr, LPG_ERR_ARG, "%s: LPG_BINARY_CHUNK=%s out of range [1, %d]", call, ce, 1 << 24);
+            return fail(b, LPG_ERR_ARG, "%s: LPG_BINARY_CHUNK=%s out of range [1, %d]", call, ce, 1 << 24);
         chunk = (int)v;
     }
-    lpg_binary *b = new lpg_binary();
+    b = new lpg_binary();
     b->device = device;
     b->count = count;
     b->m = m;
@@ -527,22 +430,20 @@ int lpg_binary_create(lpg_binary **out, int device, int64_t count, int64_t m, in
         b->tier = LPG_BATCH_TIER_GLOBAL;
         b->lds = 0;
     }
+    b->allocs = {dev_array(b->At, count * n * m), dev_array(b->L, count * m), dev_array(b->U, count * m),
+                 dev_array(b->c, count * n), dev_array(b->rows, b->nsub * 3 * m), dev_array(b->sub, b->nsub),
+                 dev_array(b->running, 1)};
+    snprintf(b->oom_what, sizeof b->oom_what, "batch of %lld problems, %lld sub-searches", (long long)count,
+             (long long)b->nsub);
     *out = b;
     return 0;
 }
 
-void lpg_binary_destroy(lpg_binary *b) {
-    if (!b) return;
-    if (b->on_device) {
-        (void)hipSetDevice(b->device);
-        release_device(b);
-    }
-    delete b;
-}
+void lpg_binary_destroy(lpg_binary *b) { destroy(b); }
 
 int lpg_binary_info(const lpg_binary *b, lpg_binary_info_t *out) {
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "lpg_binary_info: the batch is NULL");
-    if (!out) return bfail(const_cast<lpg_binary *>(b), LPG_ERR_ARG, "lpg_binary_info: out is NULL");
+    if (!b) return fail<lpg_binary>(nullptr, LPG_ERR_ARG, "lpg_binary_info: the batch is NULL");
+    if (!out) return fail(const_cast<lpg_binary *>(b), LPG_ERR_ARG, "lpg_binary_info: out is NULL");
     out->count = b->count;
     out->m = b->m;
     out->n = b->n;
@@ -559,15 +460,13 @@ int lpg_binary_info(const lpg_binary *b, lpg_binary_info_t *out) {
 int lpg_binary_load(lpg_binary *b, int64_t first, int64_t np, const double *A, int64_t ldA, const int32_t *sense,
                     const double *rhs, const double *c) {
     const char *call = "lpg_binary_load";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!A) return bfail(b, LPG_ERR_ARG, "%s: A is NULL", call);
-    if (!sense) return bfail(b, LPG_ERR_ARG, "%s: sense is NULL", call);
-    if (!rhs) return bfail(b, LPG_ERR_ARG, "%s: rhs is NULL", call);
-    if (!c) return bfail(b, LPG_ERR_ARG, "%s: c is NULL", call);
-    if (first < 0 || np < 1 || first > b->count || np > b->count - first)
-        return bfail(b, LPG_ERR_ARG, "%s: problems [%lld, %lld) outside the batch of %lld (need n >= 1)", call,
-                     (long long)first, (long long)(first + np), (long long)b->count);
-    if (ldA < b->n) return bfail(b, LPG_ERR_ARG, "%s: ldA %lld < n = %lld", call, (long long)ldA, (long long)b->n);
+    if (!b) return fail(b, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!A) return fail(b, LPG_ERR_ARG, "%s: A is NULL", call);
+    if (!sense) return fail(b, LPG_ERR_ARG, "%s: sense is NULL", call);
+    if (!rhs) return fail(b, LPG_ERR_ARG, "%s: rhs is NULL", call);
+    if (!c) return fail(b, LPG_ERR_ARG, "%s: c is NULL", call);
+    if (int rc = range_ok(b, call, first, np)) return rc;
+    if (ldA < b->n) return fail(b, LPG_ERR_ARG, "%s: ldA %lld < n = %lld", call, (long long)ldA, (long long)b->n);
     const int64_t m = b->m, n = b->n;
     const bool mx = (b->flags & LPG_BINARY_MAXIMIZE) != 0;
     const uint64_t cap = (uint64_t)1 << 52;
@@ -579,27 +478,27 @@ int lpg_binary_load(lpg_binary *b, int64_t first, int64_t np, const double *A, i
             for (int64_t j = 0; j < n; j++) {
                 const double a = A[(p * m + i) * ldA + j];
                 if (!(fabs(a) < INFINITY) || a != floor(a))
-                    return bfail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld, entry %lld is %s; entries are finite "
-                                                 "integers; nothing was loaded", call, q, (long long)i, (long long)j,
-                                 what_is(a));
+                    return fail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld, entry %lld is %s; entries are finite "
+                                                "integers; nothing was loaded", call, q, (long long)i, (long long)j,
+                                what_is(a));
                 if (fabs(a) > LPG_BINARY_SUM_CAP || (sum += (uint64_t)fabs(a)) > cap)
-                    return bfail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld, entry %lld: the row's sum of |a| exceeds "
-                                                 "the cap LPG_BINARY_SUM_CAP = 2^52; nothing was loaded", call, q,
-                                 (long long)i, (long long)j);
+                    return fail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld, entry %lld: the row's sum of |a| exceeds "
+                                                "the cap LPG_BINARY_SUM_CAP = 2^52; nothing was loaded", call, q,
+                                (long long)i, (long long)j);
                 At[(size_t)((p * n + j) * m + i)] = a + 0.0;
             }
             const int32_t sn = sense[p * m + i];
             if (sn < -1 || sn > 1)
-                return bfail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld: sense %d outside {-1, 0, 1}; nothing was "
-                                             "loaded", call, q, (long long)i, (int)sn);
+                return fail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld: sense %d outside {-1, 0, 1}; nothing was "
+                                            "loaded", call, q, (long long)i, (int)sn);
             const double r = rhs[p * m + i];
             if (!(fabs(r) < INFINITY) || r != floor(r))
-                return bfail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld: the right-hand side is %s; nothing was loaded",
-                             call, q, (long long)i, what_is(r));
+                return fail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld: the right-hand side is %s; nothing was loaded",
+                            call, q, (long long)i, what_is(r));
             if (fabs(r) > LPG_BINARY_RHS_CAP)
-                return bfail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld: the right-hand side exceeds the cap "
-                                             "LPG_BINARY_RHS_CAP = 2^53 in magnitude; nothing was loaded", call, q,
-                             (long long)i);
+                return fail(b, LPG_ERR_ARG, "%s: problem %lld, row %lld: the right-hand side exceeds the cap "
+                                            "LPG_BINARY_RHS_CAP = 2^53 in magnitude; nothing was loaded", call, q,
+                            (long long)i);
             L[(size_t)(p * m + i)] = sn < 0 ? -INFINITY : r + 0.0;
             U[(size_t)(p * m + i)] = sn > 0 ? INFINITY : r + 0.0;
         }
@@ -607,73 +506,67 @@ int lpg_binary_load(lpg_binary *b, int64_t first, int64_t np, const double *A, i
         for (int64_t j = 0; j < n; j++) {
             const double v = c[p * n + j];
             if (!(fabs(v) < INFINITY) || v != floor(v))
-                return bfail(b, LPG_ERR_ARG, "%s: problem %lld, cost %lld is %s; costs are finite integers; nothing was "
-                                             "loaded", call, q, (long long)j, what_is(v));
+                return fail(b, LPG_ERR_ARG, "%s: problem %lld, cost %lld is %s; costs are finite integers; nothing was "
+                                            "loaded", call, q, (long long)j, what_is(v));
             if (fabs(v) > LPG_BINARY_SUM_CAP || (sum += (uint64_t)fabs(v)) > cap)
-                return bfail(b, LPG_ERR_ARG, "%s: problem %lld, cost %lld: the sum of |c| exceeds the cap "
-                                             "LPG_BINARY_SUM_CAP = 2^52; nothing was loaded", call, q, (long long)j);
+                return fail(b, LPG_ERR_ARG, "%s: problem %lld, cost %lld: the sum of |c| exceeds the cap "
+                                            "LPG_BINARY_SUM_CAP = 2^52; nothing was loaded", call, q, (long long)j);
             cs[(size_t)(p * n + j)] = mx ? 0.0 - v : v + 0.0;
         }
     }
     if (int rc = ensure_device(b, call)) return rc;
-    NHIPCHK(b, hipMemcpy(b->At + first * n * m, At.data(), At.size() * sizeof(double), hipMemcpyHostToDevice));
-    NHIPCHK(b, hipMemcpy(b->L + first * m, L.data(), L.size() * sizeof(double), hipMemcpyHostToDevice));
-    NHIPCHK(b, hipMemcpy(b->U + first * m, U.data(), U.size() * sizeof(double), hipMemcpyHostToDevice));
-    NHIPCHK(b, hipMemcpy(b->c + first * n, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice));
-    for (int64_t p = 0; p < np; p++) b->have[(size_t)(first + p)] = 1;
-    b->loaded = true;
-    for (uint8_t h : b->have) b->loaded = b->loaded && h;
+    LPG_HIPCHK(b, hipMemcpy(b->At + first * n * m, At.data(), At.size() * sizeof(double), hipMemcpyHostToDevice));
+    LPG_HIPCHK(b, hipMemcpy(b->L + first * m, L.data(), L.size() * sizeof(double), hipMemcpyHostToDevice));
+    LPG_HIPCHK(b, hipMemcpy(b->U + first * m, U.data(), U.size() * sizeof(double), hipMemcpyHostToDevice));
+    LPG_HIPCHK(b, hipMemcpy(b->c + first * n, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice));
+    mark_loaded(b, first, np);
     reset_searches(b);
     return 0;
 }
 
 int lpg_binary_generate(lpg_binary *b, uint64_t seed, int kind) {
     const char *call = "lpg_binary_generate";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!b) return fail(b, LPG_ERR_ARG, "%s: the batch is NULL", call);
     if (kind != LPG_BINARY_GEN_BANDED)
-        return bfail(b, LPG_ERR_ARG, "%s: kind %d unknown (LPG_BINARY_GEN_BANDED = 0 only)", call, kind);
+        return fail(b, LPG_ERR_ARG, "%s: kind %d unknown (LPG_BINARY_GEN_BANDED = 0 only)", call, kind);
     if (int rc = ensure_device(b, call)) return rc;
     const int64_t total = b->count * (b->m + b->n);
-    NHIPCHK(b, hipMemsetAsync(b->At, 0, (size_t)(b->count * b->n * b->m) * sizeof(double), b->stream));
+    LPG_HIPCHK(b, hipMemsetAsync(b->At, 0, (size_t)(b->count * b->n * b->m) * sizeof(double), b->stream));
     hipLaunchKernelGGL(k_binary_generate, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, b->stream,
                        geo_of(b), seed);
-    NHIPCHK(b, hipGetLastError());
-    NHIPCHK(b, hipStreamSynchronize(b->stream));
-    b->have.assign((size_t)b->count, 1);
-    b->loaded = true;
+    LPG_HIPCHK(b, hipGetLastError());
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
+    mark_all_loaded(b);
     reset_searches(b);
     return 0;
 }
 
 int lpg_binary_occupancy(lpg_binary *b, int64_t *resident_waves) {
     const char *call = "lpg_binary_occupancy";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!resident_waves) return bfail(b, LPG_ERR_ARG, "%s: resident_waves is NULL", call);
-    NHIPCHK(b, hipSetDevice(b->device));
-    if (int rc = raise_lds(b, call)) return rc;
+    if (!b) return fail(b, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!resident_waves) return fail(b, LPG_ERR_ARG, "%s: resident_waves is NULL", call);
+    LPG_HIPCHK(b, hipSetDevice(b->device));
+    if (int rc = raise_lds_once(b, solve_kernel(b->rpl, b->tier), kBinaryMaxLds, call)) return rc;
     int blocks = 0, cus = 0;
-    NHIPCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, solve_kernel(b->rpl, b->tier), kBlock, (size_t)b->lds));
-    NHIPCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+    LPG_HIPCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, solve_kernel(b->rpl, b->tier), kBlock, (size_t)b->lds));
+    LPG_HIPCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
     *resident_waves = (int64_t)blocks * cus * kWaves;
     return 0;
 }
 
 int lpg_binary_solve(lpg_binary *b, int64_t max_nodes, lpg_binary_result *out) {
     const char *call = "lpg_binary_solve";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!b->loaded) {
-        int64_t q = 0;
-        while (q < b->count && b->have[(size_t)q]) q++;
-        return bfail(b, LPG_ERR_STATE, "%s: problem %lld has no data yet (lpg_binary_load or lpg_binary_generate first)",
-                     call, (long long)q);
-    }
+    if (!b) return fail(b, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!b->loaded)
+        return fail(b, LPG_ERR_STATE, "%s: problem %lld has no data yet (lpg_binary_load or lpg_binary_generate first)",
+                    call, (long long)first_unloaded(b));
     if (int rc = ensure_device(b, call)) return rc;
-    if (int rc = raise_lds(b, call)) return rc;
+    if (int rc = raise_lds_once(b, solve_kernel(b->rpl, b->tier), kBinaryMaxLds, call)) return rc;
     BinaryGeo g = geo_of(b);
     const unsigned grid = (unsigned)((b->nsub + kWaves - 1) / kWaves);
     if (b->fresh) {
         hipLaunchKernelGGL(k_binary_init, dim3(grid), dim3(kBlock), 0, b->stream, g);
-        NHIPCHK(b, hipGetLastError());
+        LPG_HIPCHK(b, hipGetLastError());
         b->fresh = false;
         b->any_running = true;
     }
@@ -684,15 +577,12 @@ int lpg_binary_solve(lpg_binary *b, int64_t max_nodes, lpg_binary_result *out) {
     while (b->any_running && !(max_nodes > 0 && used >= max_nodes)) {
         g.budget = (max_nodes > 0 && max_nodes - used < b->chunk) ? (int32_t)(max_nodes - used) : b->chunk;
         int32_t left = 0;
-        void *args[] = {&g};
-        NHIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
-        (void)hipEventRecord(b->ev0, b->stream);
-        NHIPCHK(b, hipLaunchKernel(kern, dim3(grid), dim3(kBlock), args, (size_t)b->lds, b->stream));
-        (void)hipEventRecord(b->ev1, b->stream);
-        NHIPCHK(b, hipMemcpyAsync(&left, b->running, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-        NHIPCHK(b, hipStreamSynchronize(b->stream));
+        LPG_HIPCHK(b, hipMemsetAsync(b->running, 0, sizeof(int32_t), b->stream));
+        LPG_HIPCHK(b, timed_launch(b, kern, grid, g));
+        LPG_HIPCHK(b, hipMemcpyAsync(&left, b->running, sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+        LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
         float ms = 0.0f;
-        NHIPCHK(b, hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        LPG_HIPCHK(b, hipEventElapsedTime(&ms, b->ev0, b->ev1));
         b->kernel_ms += ms;
         b->launches++;
         used += g.budget;
@@ -700,8 +590,8 @@ int lpg_binary_solve(lpg_binary *b, int64_t max_nodes, lpg_binary_result *out) {
     }
     // the split reduction, over the records copied back (lpg.h, "Split")
     std::vector<BinSub> sub((size_t)b->nsub);
-    NHIPCHK(b, hipMemcpyAsync(sub.data(), b->sub, sub.size() * sizeof(BinSub), hipMemcpyDeviceToHost, b->stream));
-    NHIPCHK(b, hipStreamSynchronize(b->stream));
+    LPG_HIPCHK(b, hipMemcpyAsync(sub.data(), b->sub, sub.size() * sizeof(BinSub), hipMemcpyDeviceToHost, b->stream));
+    LPG_HIPCHK(b, hipStreamSynchronize(b->stream));
     const int64_t S = (int64_t)1 << b->split, n = b->n;
     const bool mx = (b->flags & LPG_BINARY_MAXIMIZE) != 0;
     b->res.assign((size_t)b->count, lpg_binary_result{});
@@ -737,12 +627,10 @@ int lpg_binary_solve(lpg_binary *b, int64_t max_nodes, lpg_binary_result *out) {
 
 int lpg_binary_get(lpg_binary *b, int64_t first, int64_t np, int8_t *x) {
     const char *call = "lpg_binary_get";
-    if (!b) return bfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!x) return bfail(b, LPG_ERR_ARG, "%s: x is NULL", call);
-    if (first < 0 || np < 1 || first > b->count || np > b->count - first)
-        return bfail(b, LPG_ERR_ARG, "%s: problems [%lld, %lld) outside the batch of %lld (need n >= 1)", call,
-                     (long long)first, (long long)(first + np), (long long)b->count);
-    if (!b->solved) return bfail(b, LPG_ERR_STATE, "%s: no solve since the last load or generate", call);
+    if (!b) return fail(b, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!x) return fail(b, LPG_ERR_ARG, "%s: x is NULL", call);
+    if (int rc = range_ok(b, call, first, np)) return rc;
+    if (!b->solved) return fail(b, LPG_ERR_STATE, "%s: no solve since the last load or generate", call);
     memcpy(x, b->x.data() + first * b->n, (size_t)(np * b->n));
     return 0;
 }

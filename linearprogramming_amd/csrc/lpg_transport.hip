@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -32,6 +31,7 @@
 #include "../../include/lpg.h"
 #include "lpg_internal.h"
 #include "lpg_device.h"
+#include "lpg_host.h"
 
 namespace lpg {
 
@@ -386,56 +386,17 @@ __global__ __launch_bounds__(kBlock) void k_transport(TransportGeo g) {
 
 using namespace lpg;
 
-struct lpg_transport {
-    int device = 0;
-    int64_t count = 0, nr = 0, nc = 0;
+struct lpg_transport : BatchHost {
+    int64_t nr = 0, nc = 0;
     uint32_t flags = 0;
     int tier = LPG_BATCH_TIER_LDS, form = LPG_TRANSPORT_FORM_WAVE;
     int chunk = LPG_TRANSPORT_DEFAULT_CHUNK;
-    int64_t lds = 0;
-    bool on_device = false;       // the device side exists (made by the first call that needs it)
-    bool loaded = false;          // every problem has data (a load of the whole range, or generate)
-    std::vector<uint8_t> have;    // per problem: loaded
-    bool solved = false;
-    bool lds_raised = false;
     double *C = nullptr, *S = nullptr, *D = nullptr, *flow = nullptr, *x = nullptr, *u = nullptr, *v = nullptr;
     int32_t *cell = nullptr, *basis = nullptr, *running = nullptr;
     lpg_transport_result *res = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;     // around each solve launch
-    double kernel_ms = 0.0;
-    int64_t launches = 0;
-    char err[512] = {0};
 };
 
 namespace {
-
-thread_local char g_terr[512];
-
-int tfail(lpg_transport *t, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (t) snprintf(t->err, sizeof t->err, "%s", buf);
-    snprintf(g_terr, sizeof g_terr, "%s", buf);
-    return code;
-}
-
-#define THIPCHK(t, x)                                                                 \
-    do {                                                                              \
-        hipError_t e_ = (x);                                                          \
-        if (e_ != hipSuccess) {                                                       \
-            (void)hipGetLastError();                                                  \
-            return tfail((t), LPG_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_));   \
-        }                                                                             \
-    } while (0)
-
-bool env_is(const char *name, const char *value) {
-    const char *e = getenv(name);
-    return e && !strcmp(e, value);
-}
 
 constexpr double kTwo53 = 0x1p53;
 typedef unsigned __int128 u128;
@@ -454,71 +415,25 @@ const char *dec(u128 x, char *buf, size_t n) {
     return buf;
 }
 
-// everything ensure_device made, whole or in part
-void release_device(lpg_transport *t) {
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    for (void *p : {(void *)t->C, (void *)t->S, (void *)t->D, (void *)t->flow, (void *)t->x, (void *)t->u, (void *)t->v,
-                    (void *)t->cell, (void *)t->basis, (void *)t->running, (void *)t->res})
-        if (p) (void)hipFree(p);
-    t->C = t->S = t->D = t->flow = t->x = t->u = t->v = nullptr;
-    t->cell = t->basis = t->running = nullptr;
-    t->res = nullptr;
-    if (t->ev0) (void)hipEventDestroy(t->ev0);
-    if (t->ev1) (void)hipEventDestroy(t->ev1);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
-    t->ev0 = t->ev1 = nullptr;
-    t->stream = nullptr;
-    t->on_device = false;
-}
-
-// Device memory, stream, events: made by the first call that moves data or
-// launches, so that every refusal of create, load, generate and solve is
-// answered before the library touches a device. A setup that fails is taken
-// down again, and the next call starts it afresh.
-int ensure_device(lpg_transport *t, const char *call) {
-    hipError_t e = hipSetDevice(t->device);
+// The shared device side, and with it every problem's result "not started". A
+// setup that fails here is taken down like one that fails in the shared part.
+int device_ready(lpg_transport *t, const char *call) {
+    const bool made = !t->on_device;
+    if (int rc = ensure_device(t, call)) return rc;
+    if (!made) return 0;
+    const hipError_t e = hipMemset(t->res, 0, (size_t)t->count * sizeof(lpg_transport_result));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return tfail(t, LPG_ERR_DEVICE, "%s: hipSetDevice(%d): %s", call, t->device, hipGetErrorString(e));
-    }
-    if (t->on_device) return 0;
-    const size_t cells = (size_t)(t->count * t->nr * t->nc), nb = (size_t)(t->count * (t->nr + t->nc - 1));
-    const size_t rows = (size_t)(t->count * t->nr), cols = (size_t)(t->count * t->nc);
-    if (hipMalloc(&t->C, cells * 8) != hipSuccess || hipMalloc(&t->x, cells * 8) != hipSuccess ||
-        hipMalloc(&t->S, rows * 8) != hipSuccess || hipMalloc(&t->u, rows * 8) != hipSuccess ||
-        hipMalloc(&t->D, cols * 8) != hipSuccess || hipMalloc(&t->v, cols * 8) != hipSuccess ||
-        hipMalloc(&t->flow, nb * 8) != hipSuccess || hipMalloc(&t->cell, nb * 4) != hipSuccess ||
-        hipMalloc(&t->basis, nb * 4) != hipSuccess || hipMalloc(&t->running, 4) != hipSuccess ||
-        hipMalloc(&t->res, (size_t)t->count * sizeof(lpg_transport_result)) != hipSuccess) {
-        (void)hipGetLastError();
         release_device(t);
-        return tfail(t, LPG_ERR_OOM, "%s: hipMalloc(batch of %lld problems, %zu bytes of costs) failed", call,
-                     (long long)t->count, cells * 8);
+        return fail(t, LPG_ERR_DEVICE, "%s: stream and events: %s", call, hipGetErrorString(e));
     }
-    if ((e = hipStreamCreate(&t->stream)) != hipSuccess || (e = hipEventCreate(&t->ev0)) != hipSuccess ||
-        (e = hipEventCreate(&t->ev1)) != hipSuccess ||
-        (e = hipMemset(t->res, 0, (size_t)t->count * sizeof(lpg_transport_result))) != hipSuccess) {
-        (void)hipGetLastError();
-        release_device(t);
-        return tfail(t, LPG_ERR_DEVICE, "%s: stream and events: %s", call, hipGetErrorString(e));
-    }
-    t->on_device = true;
     return 0;
 }
 
-template <auto K>
-int launch_transport(lpg_transport *t, const TransportGeo &g, unsigned grid) {
-    if (!t->lds_raised) {
-        if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, kTransportMaxLds) != hipSuccess) {
-            (void)hipGetLastError();
-            return tfail(t, LPG_ERR_DEVICE, "lpg_transport_solve: hipFuncSetAttribute(%d bytes of LDS) failed", kTransportMaxLds);
-        }
-        t->lds_raised = true;
-    }
-    (void)hipEventRecord(t->ev0, t->stream);
-    hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), (size_t)t->lds, t->stream, g);
-    (void)hipEventRecord(t->ev1, t->stream);
-    return 0;
+const void *solve_kernel(const lpg_transport *t) {
+    if (t->form == LPG_TRANSPORT_FORM_WAVE) return (const void *)k_transport<64, LPG_BATCH_TIER_LDS>;
+    return t->tier == LPG_BATCH_TIER_LDS ? (const void *)k_transport<kBlock, LPG_BATCH_TIER_LDS>
+                                         : (const void *)k_transport<kBlock, LPG_BATCH_TIER_GLOBAL>;
 }
 
 const char *why_not_amount(double a) {
@@ -530,34 +445,35 @@ const char *why_not_amount(double a) {
 
 extern "C" {
 
-const char *lpg_transport_last_error(const lpg_transport *t) { return t ? t->err : g_terr; }
+const char *lpg_transport_last_error(const lpg_transport *t) { return t ? t->err : thread_err<lpg_transport>(); }
 
 int lpg_transport_create(lpg_transport **out, int device, int64_t count, int64_t nr, int64_t nc, uint32_t flags) {
     const char *call = "lpg_transport_create";
-    if (!out) return tfail(nullptr, LPG_ERR_ARG, "%s: out is NULL", call);
+    lpg_transport *t = nullptr;           // not made yet: the refusals below go to the thread's buffer only
+    if (!out) return fail(t, LPG_ERR_ARG, "%s: out is NULL", call);
     *out = nullptr;
     if (count < 1 || nr < 1 || nc < 1)
-        return tfail(nullptr, LPG_ERR_ARG, "%s: bad shape count=%lld nr=%lld nc=%lld (need count >= 1, nr >= 1, nc >= 1)", call,
-                     (long long)count, (long long)nr, (long long)nc);
+        return fail(t, LPG_ERR_ARG, "%s: bad shape count=%lld nr=%lld nc=%lld (need count >= 1, nr >= 1, nc >= 1)", call,
+                    (long long)count, (long long)nr, (long long)nc);
     if (nr > LPG_TRANSPORT_MAX_NODES || nc > LPG_TRANSPORT_MAX_NODES || nr + nc > LPG_TRANSPORT_MAX_NODES)
-        return tfail(nullptr, LPG_ERR_ARG, "%s: nr + nc = %lld + %lld exceeds LPG_TRANSPORT_MAX_NODES = %d", call,
-                     (long long)nr, (long long)nc, LPG_TRANSPORT_MAX_NODES);
+        return fail(t, LPG_ERR_ARG, "%s: nr + nc = %lld + %lld exceeds LPG_TRANSPORT_MAX_NODES = %d", call,
+                    (long long)nr, (long long)nc, LPG_TRANSPORT_MAX_NODES);
     if (flags & ~(uint32_t)(LPG_TRANSPORT_MAXIMIZE | LPG_TRANSPORT_START_NORTHWEST))
-        return tfail(nullptr, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_TRANSPORT_MAXIMIZE, "
-                                           "LPG_TRANSPORT_START_NORTHWEST)", call, flags);
-    if (device < 0) return tfail(nullptr, LPG_ERR_ARG, "%s: device %d", call, device);
+        return fail(t, LPG_ERR_ARG, "%s: flags 0x%x not supported (LPG_TRANSPORT_MAXIMIZE, "
+                                    "LPG_TRANSPORT_START_NORTHWEST)", call, flags);
+    if (device < 0) return fail(t, LPG_ERR_ARG, "%s: device %d", call, device);
     if (count > (int64_t)0x7fffffff / (nr * nc) || count > (int64_t)0x7fffffff / (nr + nc))
-        return tfail(nullptr, LPG_ERR_ARG, "%s: count * nr * nc = %lld x %lld x %lld exceeds 2^31 - 1", call, (long long)count,
-                     (long long)nr, (long long)nc);
+        return fail(t, LPG_ERR_ARG, "%s: count * nr * nc = %lld x %lld x %lld exceeds 2^31 - 1", call, (long long)count,
+                    (long long)nr, (long long)nc);
     int chunk = LPG_TRANSPORT_DEFAULT_CHUNK;
     if (const char *e = getenv("LPG_TRANSPORT_CHUNK")) {
         char *end = nullptr;
         const long c = strtol(e, &end, 10);
         if (end == e || *end || c < 1 || c > (1 << 30))
-            return tfail(nullptr, LPG_ERR_ARG, "%s: LPG_TRANSPORT_CHUNK=\"%s\" is not an integer in 1..2^30", call, e);
+            return fail(t, LPG_ERR_ARG, "%s: LPG_TRANSPORT_CHUNK=\"%s\" is not an integer in 1..2^30", call, e);
         chunk = (int)c;
     }
-    lpg_transport *t = new lpg_transport();
+    t = new lpg_transport();
     t->device = device;
     t->count = count;
     t->nr = nr;
@@ -583,22 +499,21 @@ int lpg_transport_create(lpg_transport **out, int device, int64_t count, int64_t
             t->lds = nbytes;                   // 4096 nodes: 128 KiB
         }
     }
+    const int64_t cells = count * nr * nc, nb = count * (nr + nc - 1);
+    t->allocs = {dev_array(t->C, cells), dev_array(t->x, cells), dev_array(t->S, count * nr), dev_array(t->u, count * nr),
+                 dev_array(t->D, count * nc), dev_array(t->v, count * nc), dev_array(t->flow, nb), dev_array(t->cell, nb),
+                 dev_array(t->basis, nb), dev_array(t->running, 1), dev_array(t->res, count)};
+    snprintf(t->oom_what, sizeof t->oom_what, "batch of %lld problems, %zu bytes of costs", (long long)count,
+             (size_t)cells * 8);
     *out = t;
     return 0;
 }
 
-void lpg_transport_destroy(lpg_transport *t) {
-    if (!t) return;
-    if (t->on_device) {
-        (void)hipSetDevice(t->device);
-        release_device(t);
-    }
-    delete t;
-}
+void lpg_transport_destroy(lpg_transport *t) { destroy(t); }
 
 int lpg_transport_info(const lpg_transport *t, lpg_transport_info_t *out) {
-    if (!t) return tfail(nullptr, LPG_ERR_ARG, "lpg_transport_info: the batch is NULL");
-    if (!out) return tfail(const_cast<lpg_transport *>(t), LPG_ERR_ARG, "lpg_transport_info: out is NULL");
+    if (!t) return fail<lpg_transport>(nullptr, LPG_ERR_ARG, "lpg_transport_info: the batch is NULL");
+    if (!out) return fail(const_cast<lpg_transport *>(t), LPG_ERR_ARG, "lpg_transport_info: out is NULL");
     out->count = t->count;
     out->nr = t->nr;
     out->nc = t->nc;
@@ -615,14 +530,12 @@ int lpg_transport_info(const lpg_transport *t, lpg_transport_info_t *out) {
 int lpg_transport_load(lpg_transport *t, int64_t first, int64_t n, const double *costs, int64_t ld, const double *supply,
                        const double *demand) {
     const char *call = "lpg_transport_load";
-    if (!t) return tfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!costs) return tfail(t, LPG_ERR_ARG, "%s: costs is NULL", call);
-    if (!supply) return tfail(t, LPG_ERR_ARG, "%s: supply is NULL", call);
-    if (!demand) return tfail(t, LPG_ERR_ARG, "%s: demand is NULL", call);
-    if (first < 0 || n < 1 || first > t->count || n > t->count - first)
-        return tfail(t, LPG_ERR_ARG, "%s: problems [%lld, %lld) outside the batch of %lld (need n >= 1)", call,
-                     (long long)first, (long long)(first + n), (long long)t->count);
-    if (ld < t->nc) return tfail(t, LPG_ERR_ARG, "%s: ld %lld < nc = %lld", call, (long long)ld, (long long)t->nc);
+    if (!t) return fail(t, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!costs) return fail(t, LPG_ERR_ARG, "%s: costs is NULL", call);
+    if (!supply) return fail(t, LPG_ERR_ARG, "%s: supply is NULL", call);
+    if (!demand) return fail(t, LPG_ERR_ARG, "%s: demand is NULL", call);
+    if (int rc = range_ok(t, call, first, n)) return rc;
+    if (ld < t->nc) return fail(t, LPG_ERR_ARG, "%s: ld %lld < nc = %lld", call, (long long)ld, (long long)t->nc);
     const int64_t nr = t->nr, nc = t->nc;
     const bool mx = (t->flags & LPG_TRANSPORT_MAXIMIZE) != 0;
     std::vector<double> stage((size_t)(n * nr * nc));
@@ -636,8 +549,8 @@ int lpg_transport_load(lpg_transport *t, int64_t first, int64_t n, const double 
                 const char *why = c != c ? "NaN" : (c == INFINITY || c == -INFINITY) ? "infinite" : c != floor(c) ? "not an integer"
                                   : fabs(c) > LPG_TRANSPORT_COST_CAP ? "above the cap 2^40 in magnitude" : nullptr;
                 if (why)
-                    return tfail(t, LPG_ERR_ARG, "%s: problem %lld, cost (%lld, %lld) is %s; costs are integers with |c| <= "
-                                                 "2^40; nothing was loaded", call, P, (long long)i, (long long)j, why);
+                    return fail(t, LPG_ERR_ARG, "%s: problem %lld, cost (%lld, %lld) is %s; costs are integers with |c| <= "
+                                                "2^40; nothing was loaded", call, P, (long long)i, (long long)j, why);
                 cmax = fabs(c) > cmax ? fabs(c) : cmax;
                 stage[(size_t)((p * nr + i) * nc + j)] = mx ? 0.0 - c : c + 0.0;
             }
@@ -645,81 +558,75 @@ int lpg_transport_load(lpg_transport *t, int64_t first, int64_t n, const double 
         for (int64_t i = 0; i < nr; i++) {
             const double a = supply[p * nr + i];
             if (const char *why = why_not_amount(a))
-                return tfail(t, LPG_ERR_ARG, "%s: problem %lld, supply %lld is %s; supplies are integers in 0..2^53; nothing "
-                                             "was loaded", call, P, (long long)i, why);
+                return fail(t, LPG_ERR_ARG, "%s: problem %lld, supply %lld is %s; supplies are integers in 0..2^53; nothing "
+                                            "was loaded", call, P, (long long)i, why);
             ss += (u128)(uint64_t)a;
         }
         for (int64_t j = 0; j < nc; j++) {
             const double a = demand[p * nc + j];
             if (const char *why = why_not_amount(a))
-                return tfail(t, LPG_ERR_ARG, "%s: problem %lld, demand %lld is %s; demands are integers in 0..2^53; nothing "
-                                             "was loaded", call, P, (long long)j, why);
+                return fail(t, LPG_ERR_ARG, "%s: problem %lld, demand %lld is %s; demands are integers in 0..2^53; nothing "
+                                            "was loaded", call, P, (long long)j, why);
             sd += (u128)(uint64_t)a;
         }
         if (ss != sd)
-            return tfail(t, LPG_ERR_ARG, "%s: problem %lld is not balanced: the supplies sum to %s, the demands to %s; nothing "
-                                         "was loaded", call, P, dec(ss, b1, sizeof b1), dec(sd, b2, sizeof b2));
+            return fail(t, LPG_ERR_ARG, "%s: problem %lld is not balanced: the supplies sum to %s, the demands to %s; nothing "
+                                        "was loaded", call, P, dec(ss, b1, sizeof b1), dec(sd, b2, sizeof b2));
         if (ss > ((u128)1 << 53))
-            return tfail(t, LPG_ERR_ARG, "%s: problem %lld: the supplies sum to %s, above 2^53; nothing was loaded", call, P,
-                         dec(ss, b1, sizeof b1));
+            return fail(t, LPG_ERR_ARG, "%s: problem %lld: the supplies sum to %s, above 2^53; nothing was loaded", call, P,
+                        dec(ss, b1, sizeof b1));
         if ((u128)(uint64_t)cmax * ss > ((u128)1 << 53))
-            return tfail(t, LPG_ERR_ARG, "%s: problem %lld: max |c| x sum of supplies = %s x %s exceeds 2^53; nothing was "
-                                         "loaded", call, P, dec((u128)(uint64_t)cmax, b1, sizeof b1), dec(ss, b2, sizeof b2));
+            return fail(t, LPG_ERR_ARG, "%s: problem %lld: max |c| x sum of supplies = %s x %s exceeds 2^53; nothing was "
+                                        "loaded", call, P, dec((u128)(uint64_t)cmax, b1, sizeof b1), dec(ss, b2, sizeof b2));
     }
-    if (int rc = ensure_device(t, call)) return rc;
-    THIPCHK(t, hipMemcpy(t->C + first * nr * nc, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
-    THIPCHK(t, hipMemcpy(t->S + first * nr, supply, (size_t)(n * nr) * sizeof(double), hipMemcpyHostToDevice));
-    THIPCHK(t, hipMemcpy(t->D + first * nc, demand, (size_t)(n * nc) * sizeof(double), hipMemcpyHostToDevice));
-    THIPCHK(t, hipMemset(t->res + first, 0, (size_t)n * sizeof(lpg_transport_result)));    // not started
-    for (int64_t p = 0; p < n; p++) t->have[(size_t)(first + p)] = 1;
-    t->loaded = true;
-    for (uint8_t h : t->have) t->loaded = t->loaded && h;
+    if (int rc = device_ready(t, call)) return rc;
+    LPG_HIPCHK(t, hipMemcpy(t->C + first * nr * nc, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+    LPG_HIPCHK(t, hipMemcpy(t->S + first * nr, supply, (size_t)(n * nr) * sizeof(double), hipMemcpyHostToDevice));
+    LPG_HIPCHK(t, hipMemcpy(t->D + first * nc, demand, (size_t)(n * nc) * sizeof(double), hipMemcpyHostToDevice));
+    LPG_HIPCHK(t, hipMemset(t->res + first, 0, (size_t)n * sizeof(lpg_transport_result)));    // not started
+    mark_loaded(t, first, n);
     t->solved = false;
     return 0;
 }
 
 int lpg_transport_generate(lpg_transport *t, uint64_t seed, int64_t range, int64_t qmax) {
     const char *call = "lpg_transport_generate";
-    if (!t) return tfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!t) return fail(t, LPG_ERR_ARG, "%s: the batch is NULL", call);
     if (range < 1 || range > ((int64_t)1 << 40) + 1)
-        return tfail(t, LPG_ERR_ARG, "%s: range %lld outside 1..2^40 + 1", call, (long long)range);
+        return fail(t, LPG_ERR_ARG, "%s: range %lld outside 1..2^40 + 1", call, (long long)range);
     if (qmax < 1 || qmax > ((int64_t)1 << 53))
-        return tfail(t, LPG_ERR_ARG, "%s: qmax %lld outside 1..2^53", call, (long long)qmax);
+        return fail(t, LPG_ERR_ARG, "%s: qmax %lld outside 1..2^53", call, (long long)qmax);
     const int64_t side = t->nr > t->nc ? t->nr : t->nc;
     // the larger sum is at most side * qmax; costs reach range - 1
     if ((u128)side * (u128)qmax > ((u128)1 << 53) || (u128)(range - 1) * (u128)side * (u128)qmax > ((u128)1 << 53))
-        return tfail(t, LPG_ERR_ARG, "%s: (range - 1) x max(nr, nc) x qmax = %lld x %lld x %lld may exceed 2^53", call,
-                     (long long)(range - 1), (long long)side, (long long)qmax);
-    if (int rc = ensure_device(t, call)) return rc;
+        return fail(t, LPG_ERR_ARG, "%s: (range - 1) x max(nr, nc) x qmax = %lld x %lld x %lld may exceed 2^53", call,
+                    (long long)(range - 1), (long long)side, (long long)qmax);
+    if (int rc = device_ready(t, call)) return rc;
     const int64_t per = t->nr * t->nc, total = t->count * per;
     hipLaunchKernelGGL(k_transport_gen_costs, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, t->stream,
                        t->C, t->count, per, seed, (double)range, (t->flags & LPG_TRANSPORT_MAXIMIZE) ? 1 : 0);
     hipLaunchKernelGGL(k_transport_gen_amounts, dim3((unsigned)((t->count + kBlock - 1) / kBlock)), dim3(kBlock), 0, t->stream,
                        t->S, t->D, t->count, (int)t->nr, (int)t->nc, seed, (double)qmax);
-    THIPCHK(t, hipGetLastError());
-    THIPCHK(t, hipMemsetAsync(t->res, 0, (size_t)t->count * sizeof(lpg_transport_result), t->stream));
-    THIPCHK(t, hipStreamSynchronize(t->stream));
-    t->have.assign((size_t)t->count, 1);
-    t->loaded = true;
+    LPG_HIPCHK(t, hipGetLastError());
+    LPG_HIPCHK(t, hipMemsetAsync(t->res, 0, (size_t)t->count * sizeof(lpg_transport_result), t->stream));
+    LPG_HIPCHK(t, hipStreamSynchronize(t->stream));
+    mark_all_loaded(t);
     t->solved = false;
     return 0;
 }
 
 int lpg_transport_solve(lpg_transport *t, int64_t max_iters, int rule, lpg_transport_result *out) {
     const char *call = "lpg_transport_solve";
-    if (!t) return tfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!t) return fail(t, LPG_ERR_ARG, "%s: the batch is NULL", call);
     if (max_iters < 1)
-        return tfail(t, LPG_ERR_ARG, "%s: max_iters = %lld (need >= 1: the rules do not exclude cycling, so there is no "
-                                     "unbounded form)", call, (long long)max_iters);
+        return fail(t, LPG_ERR_ARG, "%s: max_iters = %lld (need >= 1: the rules do not exclude cycling, so there is no "
+                                    "unbounded form)", call, (long long)max_iters);
     if (rule != LPG_RULE_DANTZIG && rule != LPG_RULE_BLAND)
-        return tfail(t, LPG_ERR_ARG, "%s: rule %d (LPG_RULE_DANTZIG or LPG_RULE_BLAND)", call, rule);
-    if (!t->loaded) {
-        int64_t q = 0;
-        while (q < t->count && t->have[(size_t)q]) q++;
-        return tfail(t, LPG_ERR_STATE, "%s: problem %lld has no data yet (lpg_transport_load or lpg_transport_generate first)",
-                     call, (long long)q);
-    }
-    if (int rc = ensure_device(t, call)) return rc;
+        return fail(t, LPG_ERR_ARG, "%s: rule %d (LPG_RULE_DANTZIG or LPG_RULE_BLAND)", call, rule);
+    if (!t->loaded)
+        return fail(t, LPG_ERR_STATE, "%s: problem %lld has no data yet (lpg_transport_load or lpg_transport_generate first)",
+                    call, (long long)first_unloaded(t));
+    if (int rc = device_ready(t, call)) return rc;
     TransportGeo g{};
     g.C = t->C;
     g.S = t->S;
@@ -740,54 +647,47 @@ int lpg_transport_solve(lpg_transport *t, int64_t max_iters, int rule, lpg_trans
     g.rule = rule;
     t->kernel_ms = 0.0;
     t->launches = 0;
+    const void *kern = solve_kernel(t);
+    const unsigned grid =
+        (unsigned)(t->form == LPG_TRANSPORT_FORM_WAVE ? (t->count + kTransportWaves - 1) / kTransportWaves : t->count);
     // At most `chunk` iterations per problem and launch; the host relaunches while a problem is unfinished and the
     // call has budget left. The last launch of the call turns "out of budget" into LPG_ITER_LIMIT.
     for (int64_t remaining = max_iters;;) {
         g.budget = (int32_t)(remaining < t->chunk ? remaining : t->chunk);
         g.final = g.budget == remaining;
-        THIPCHK(t, hipMemsetAsync(t->running, 0, sizeof(int32_t), t->stream));
-        int rc;
-        if (t->form == LPG_TRANSPORT_FORM_WAVE)
-            rc = launch_transport<k_transport<64, LPG_BATCH_TIER_LDS>>(
-                t, g, (unsigned)((t->count + kTransportWaves - 1) / kTransportWaves));
-        else if (t->tier == LPG_BATCH_TIER_LDS)
-            rc = launch_transport<k_transport<kBlock, LPG_BATCH_TIER_LDS>>(t, g, (unsigned)t->count);
-        else
-            rc = launch_transport<k_transport<kBlock, LPG_BATCH_TIER_GLOBAL>>(t, g, (unsigned)t->count);
-        if (rc) return rc;
-        THIPCHK(t, hipGetLastError());
-        THIPCHK(t, hipStreamSynchronize(t->stream));
+        LPG_HIPCHK(t, hipMemsetAsync(t->running, 0, sizeof(int32_t), t->stream));
+        if (int rc = raise_lds_once(t, kern, kTransportMaxLds, call)) return rc;
+        LPG_HIPCHK(t, timed_launch(t, kern, grid, g));
+        LPG_HIPCHK(t, hipStreamSynchronize(t->stream));
         float ms = 0.0f;
-        THIPCHK(t, hipEventElapsedTime(&ms, t->ev0, t->ev1));
+        LPG_HIPCHK(t, hipEventElapsedTime(&ms, t->ev0, t->ev1));
         t->kernel_ms += ms;
         t->launches++;
         remaining -= g.budget;
         if (g.final) break;
         int32_t running = 0;
-        THIPCHK(t, hipMemcpy(&running, t->running, sizeof running, hipMemcpyDeviceToHost));
+        LPG_HIPCHK(t, hipMemcpy(&running, t->running, sizeof running, hipMemcpyDeviceToHost));
         if (!running) break;
     }
     t->solved = true;
-    if (out) THIPCHK(t, hipMemcpy(out, t->res, (size_t)t->count * sizeof(lpg_transport_result), hipMemcpyDeviceToHost));
+    if (out) LPG_HIPCHK(t, hipMemcpy(out, t->res, (size_t)t->count * sizeof(lpg_transport_result), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int lpg_transport_get(lpg_transport *t, int64_t first, int64_t n, double *x, double *u, double *v, int64_t *basis) {
     const char *call = "lpg_transport_get";
-    if (!t) return tfail(nullptr, LPG_ERR_ARG, "%s: the batch is NULL", call);
-    if (!x && !u && !v && !basis) return tfail(t, LPG_ERR_ARG, "%s: x, u, v and basis are all NULL", call);
-    if (first < 0 || n < 1 || first > t->count || n > t->count - first)
-        return tfail(t, LPG_ERR_ARG, "%s: problems [%lld, %lld) outside the batch of %lld (need n >= 1)", call,
-                     (long long)first, (long long)(first + n), (long long)t->count);
-    if (!t->solved) return tfail(t, LPG_ERR_STATE, "%s: no solve since the last load or generate", call);
-    THIPCHK(t, hipSetDevice(t->device));
+    if (!t) return fail(t, LPG_ERR_ARG, "%s: the batch is NULL", call);
+    if (!x && !u && !v && !basis) return fail(t, LPG_ERR_ARG, "%s: x, u, v and basis are all NULL", call);
+    if (int rc = range_ok(t, call, first, n)) return rc;
+    if (!t->solved) return fail(t, LPG_ERR_STATE, "%s: no solve since the last load or generate", call);
+    LPG_HIPCHK(t, hipSetDevice(t->device));
     const int64_t nr = t->nr, nc = t->nc, nb = nr + nc - 1;
-    if (x) THIPCHK(t, hipMemcpy(x, t->x + first * nr * nc, (size_t)(n * nr * nc) * sizeof(double), hipMemcpyDeviceToHost));
-    if (u) THIPCHK(t, hipMemcpy(u, t->u + first * nr, (size_t)(n * nr) * sizeof(double), hipMemcpyDeviceToHost));
-    if (v) THIPCHK(t, hipMemcpy(v, t->v + first * nc, (size_t)(n * nc) * sizeof(double), hipMemcpyDeviceToHost));
+    if (x) LPG_HIPCHK(t, hipMemcpy(x, t->x + first * nr * nc, (size_t)(n * nr * nc) * sizeof(double), hipMemcpyDeviceToHost));
+    if (u) LPG_HIPCHK(t, hipMemcpy(u, t->u + first * nr, (size_t)(n * nr) * sizeof(double), hipMemcpyDeviceToHost));
+    if (v) LPG_HIPCHK(t, hipMemcpy(v, t->v + first * nc, (size_t)(n * nc) * sizeof(double), hipMemcpyDeviceToHost));
     if (basis) {
         std::vector<int32_t> b32((size_t)(n * nb));
-        THIPCHK(t, hipMemcpy(b32.data(), t->basis + first * nb, b32.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        LPG_HIPCHK(t, hipMemcpy(b32.data(), t->basis + first * nb, b32.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         for (size_t e = 0; e < b32.size(); e++) basis[e] = b32[e];
     }
     return 0;

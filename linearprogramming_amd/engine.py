@@ -21,18 +21,20 @@ class LPGError(RuntimeError):
     pass
 
 
+class _HasStatus:
+    @property
+    def status_name(self) -> str:
+        return L.STATUS_NAMES.get(self.status, str(self.status))
+
+
 @dataclass
-class SolveResult:
+class SolveResult(_HasStatus):
     status: int
     pivots: int
     objective: float
     entering: int
     leaving: int
     rule: int
-
-    @property
-    def status_name(self) -> str:
-        return L.STATUS_NAMES.get(self.status, str(self.status))
 
 
 @dataclass
@@ -89,25 +91,31 @@ def device_count() -> int:
     return n.value
 
 
-class Engine:
-    """One rank's engine for an m x ncols (= N+1) tableau."""
+class _Handle:
+    """What every handle on a library object shares. A subclass names the C prefix of its calls (``lpg_assign``:
+    lpg_assign_destroy, lpg_assign_last_error, lpg_assign_info) and its info struct; the handle itself is ``_h``."""
 
-    def __init__(self, m: int, ncols: int, device: int = 0, world: int = 1, rank: int = 0, flags: int = 0,
-                 lib=None):
+    _prefix = None
+    _info_type = None
+    _h = None
+
+    def _open(self, lib, handle=None):
+        """The library, and the handle: null until _create fills it, or one the library already made."""
         self.lib = lib if lib is not None else L.load()
-        self._ctx = ctypes.c_void_p()
-        rc = self.lib.lpg_create_dist(ctypes.byref(self._ctx), device, world, rank, m, ncols, flags)
-        if rc != 0:
-            raise LPGError(f"lpg_create_dist rc={rc}: {self.lib.lpg_last_error(None).decode()}")
-        self.m, self.ncols, self.world, self.rank = m, ncols, world, rank
-        self.nobj = 2 if flags & L.FLAG_BIG_M else 1
-        self._keep = []   # ctypes callbacks kept alive
+        self._h = ctypes.c_void_p() if handle is None else handle
 
-    # -- lifecycle -------------------------------------------------------
+    def _call(self, suffix):
+        return getattr(self.lib, f"{self._prefix}_{suffix}")
+
+    def _create(self, name, *args):
+        rc = getattr(self.lib, name)(ctypes.byref(self._h), *args)
+        if rc != 0:
+            raise LPGError(f"{name} rc={rc}: {self._call('last_error')(None).decode()}")
+
     def close(self):
-        if self._ctx:
-            self.lib.lpg_destroy(self._ctx)
-            self._ctx = ctypes.c_void_p()
+        if self._h:
+            self._call("destroy")(self._h)
+            self._h = ctypes.c_void_p()
 
     def __enter__(self):
         return self
@@ -123,20 +131,34 @@ class Engine:
 
     def _check(self, rc, what):
         if rc < 0:
-            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_last_error(self._ctx).decode()}")
+            raise LPGError(f"{what} rc={rc}: {self._call('last_error')(self._h).decode()}")
         return rc
 
     @property
-    def info(self) -> L.Info:
-        i = L.Info()
-        self._check(self.lib.lpg_info(self._ctx, ctypes.byref(i)), "lpg_info")
+    def info(self):
+        i = self._info_type()
+        self._check(self._call("info")(self._h, ctypes.byref(i)), f"{self._prefix}_info")
         return i
+
+
+class Engine(_Handle):
+    """One rank's engine for an m x ncols (= N+1) tableau."""
+
+    _prefix, _info_type = "lpg", L.Info
+
+    def __init__(self, m: int, ncols: int, device: int = 0, world: int = 1, rank: int = 0, flags: int = 0,
+                 lib=None):
+        self._open(lib)
+        self._create("lpg_create_dist", device, world, rank, m, ncols, flags)
+        self.m, self.ncols, self.world, self.rank = m, ncols, world, rank
+        self.nobj = 2 if flags & L.FLAG_BIG_M else 1
+        self._keep = []   # ctypes callbacks kept alive
 
     # -- communication ---------------------------------------------------
     def comm_init_rccl(self, uid: bytes):
         buf = ctypes.create_string_buffer(bytes(uid), len(uid))
         with _stdout_to_stderr():
-            rc = self.lib.lpg_comm_init_rccl(self._ctx, buf, len(uid))
+            rc = self.lib.lpg_comm_init_rccl(self._h, buf, len(uid))
         self._check(rc, "lpg_comm_init_rccl")
 
     @staticmethod
@@ -173,34 +195,34 @@ class Engine:
 
         ops = L.HostCommOps(None, L.ALLGATHER_FN(_ag), L.ALLREDUCE_FN(_ar))
         self._keep += [ops, _ag, _ar]
-        self._check(self.lib.lpg_comm_init_host(self._ctx, ctypes.byref(ops)), "lpg_comm_init_host")
+        self._check(self.lib.lpg_comm_init_host(self._h, ctypes.byref(ops)), "lpg_comm_init_host")
 
     # owner-push exchange (include/lpg.h): after a communicator
     def push_handle(self) -> bytes:
         buf = ctypes.create_string_buffer(64)
-        self._check(self.lib.lpg_comm_push_handle(self._ctx, buf, 64), "lpg_comm_push_handle")
+        self._check(self.lib.lpg_comm_push_handle(self._h, buf, 64), "lpg_comm_push_handle")
         return buf.raw
 
     def push_base(self) -> int:
         p = ctypes.c_void_p()
-        self._check(self.lib.lpg_comm_push_base(self._ctx, ctypes.byref(p)), "lpg_comm_push_base")
+        self._check(self.lib.lpg_comm_push_base(self._h, ctypes.byref(p)), "lpg_comm_push_base")
         return p.value
 
     def comm_init_push(self, handles):
         """handles: every rank's push_handle(), in rank order."""
         blob = b"".join(bytes(h) for h in handles)
         buf = ctypes.create_string_buffer(blob, len(blob))
-        self._check(self.lib.lpg_comm_init_push(self._ctx, buf, len(blob)), "lpg_comm_init_push")
+        self._check(self.lib.lpg_comm_init_push(self._h, buf, len(blob)), "lpg_comm_init_push")
 
     def comm_init_push_local(self, bases):
         """bases: every rank's push_base() (ranks of one process), in rank order."""
         arr = (ctypes.c_void_p * len(bases))(*bases)
-        self._check(self.lib.lpg_comm_init_push_local(self._ctx, arr, len(bases)), "lpg_comm_init_push_local")
+        self._check(self.lib.lpg_comm_init_push_local(self._h, arr, len(bases)), "lpg_comm_init_push_local")
 
     # -- loading ---------------------------------------------------------
     def load_rows(self, row0: int, rows: np.ndarray):
         rows = np.ascontiguousarray(rows, dtype=np.float64)
-        self._check(self.lib.lpg_load_rows(self._ctx, row0, rows.shape[0],
+        self._check(self.lib.lpg_load_rows(self._h, row0, rows.shape[0],
                                            rows.ctypes.data_as(L.c_double_p), rows.shape[1]), "lpg_load_rows")
 
     def load_tableau(self, T: np.ndarray, basis=None):
@@ -211,107 +233,107 @@ class Engine:
 
     def set_basis(self, basis):
         b = np.ascontiguousarray(basis, dtype=np.int64)
-        self._check(self.lib.lpg_set_basis(self._ctx, b.ctypes.data_as(L.c_int64_p)), "lpg_set_basis")
+        self._check(self.lib.lpg_set_basis(self._h, b.ctypes.data_as(L.c_int64_p)), "lpg_set_basis")
 
     def set_objective(self, c):
         c = np.ascontiguousarray(c, dtype=np.float64)
-        self._check(self.lib.lpg_set_objective(self._ctx, c.ctypes.data_as(L.c_double_p)), "lpg_set_objective")
+        self._check(self.lib.lpg_set_objective(self._h, c.ctypes.data_as(L.c_double_p)), "lpg_set_objective")
 
     def set_tolerances(self, eps_piv=1e-9, eps_opt=1e-9):
-        self._check(self.lib.lpg_set_tolerances(self._ctx, eps_piv, eps_opt), "lpg_set_tolerances")
+        self._check(self.lib.lpg_set_tolerances(self._h, eps_piv, eps_opt), "lpg_set_tolerances")
 
     def set_active_columns(self, nact: int):
-        self._check(self.lib.lpg_set_active_columns(self._ctx, nact), "lpg_set_active_columns")
+        self._check(self.lib.lpg_set_active_columns(self._h, nact), "lpg_set_active_columns")
 
     def generate(self, n: int, seed: int = 20220518, kind: int = L.GEN_DENSE):
-        self._check(self.lib.lpg_generate(self._ctx, n, seed, kind), "lpg_generate")
+        self._check(self.lib.lpg_generate(self._h, n, seed, kind), "lpg_generate")
 
     # -- pivoting --------------------------------------------------------
     def solve(self, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> SolveResult:
         r = L.Result()
-        self._check(self.lib.lpg_solve(self._ctx, max_pivots, rule, ctypes.byref(r)), "lpg_solve")
+        self._check(self.lib.lpg_solve(self._h, max_pivots, rule, ctypes.byref(r)), "lpg_solve")
         return _res(r)
 
     def enqueue(self, npivots: int, rule: int = L.RULE_DANTZIG):
-        self._check(self.lib.lpg_enqueue(self._ctx, npivots, rule), "lpg_enqueue")
+        self._check(self.lib.lpg_enqueue(self._h, npivots, rule), "lpg_enqueue")
 
     def sync(self) -> SolveResult:
         r = L.Result()
-        self._check(self.lib.lpg_sync(self._ctx, ctypes.byref(r)), "lpg_sync")
+        self._check(self.lib.lpg_sync(self._h, ctypes.byref(r)), "lpg_sync")
         return _res(r)
 
     def pivot(self, k: int, r: int):
-        self._check(self.lib.lpg_pivot(self._ctx, k, r), "lpg_pivot")
+        self._check(self.lib.lpg_pivot(self._h, k, r), "lpg_pivot")
 
     def solve_two_phase(self, art_first: int, cost=None, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG):
         cp = None if cost is None else np.ascontiguousarray(cost, dtype=np.float64).ctypes.data_as(L.c_double_p)
         r = L.Result()
-        self._check(self.lib.lpg_solve_two_phase(self._ctx, art_first, cp, max_pivots, rule, ctypes.byref(r)),
+        self._check(self.lib.lpg_solve_two_phase(self._h, art_first, cp, max_pivots, rule, ctypes.byref(r)),
                     "lpg_solve_two_phase")
         return _res(r)
 
     def set_objective_m(self, cM):
         c = np.ascontiguousarray(cM, dtype=np.float64)
-        self._check(self.lib.lpg_set_objective_m(self._ctx, c.ctypes.data_as(L.c_double_p)), "lpg_set_objective_m")
+        self._check(self.lib.lpg_set_objective_m(self._h, c.ctypes.data_as(L.c_double_p)), "lpg_set_objective_m")
 
     def solve_big_m(self, art_first: int, cost=None, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG):
         cp = None if cost is None else np.ascontiguousarray(cost, dtype=np.float64).ctypes.data_as(L.c_double_p)
         r = L.Result()
-        self._check(self.lib.lpg_solve_big_m(self._ctx, art_first, cp, max_pivots, rule, ctypes.byref(r)),
+        self._check(self.lib.lpg_solve_big_m(self._h, art_first, cp, max_pivots, rule, ctypes.byref(r)),
                     "lpg_solve_big_m")
         return _res(r)
 
     def solve_dual(self, max_pivots: int = 1 << 40) -> SolveResult:
         r = L.Result()
-        self._check(self.lib.lpg_solve_dual(self._ctx, max_pivots, ctypes.byref(r)), "lpg_solve_dual")
+        self._check(self.lib.lpg_solve_dual(self._h, max_pivots, ctypes.byref(r)), "lpg_solve_dual")
         return _res(r)
 
     def reserve_log(self, n: int):
-        self._check(self.lib.lpg_reserve_log(self._ctx, n), "lpg_reserve_log")
+        self._check(self.lib.lpg_reserve_log(self._h, n), "lpg_reserve_log")
 
     def prepare(self, rule: int = L.RULE_DANTZIG):
         """Build the replayed pivot graph now (no pivots run; include/lpg.h lpg_prepare)."""
-        self._check(self.lib.lpg_prepare(self._ctx, rule), "lpg_prepare")
+        self._check(self.lib.lpg_prepare(self._h, rule), "lpg_prepare")
 
     def device_sync(self):
-        self._check(self.lib.lpg_device_sync(self._ctx), "lpg_device_sync")
+        self._check(self.lib.lpg_device_sync(self._h), "lpg_device_sync")
 
     # -- readout ---------------------------------------------------------
     def get_rows(self, row0: int, nrows: int) -> np.ndarray:
         out = np.zeros((nrows, self.ncols), dtype=np.float64)
-        self._check(self.lib.lpg_get_rows(self._ctx, row0, nrows, out.ctypes.data_as(L.c_double_p), self.ncols),
+        self._check(self.lib.lpg_get_rows(self._h, row0, nrows, out.ctypes.data_as(L.c_double_p), self.ncols),
                     "lpg_get_rows")
         return out
 
     def get_basis(self) -> np.ndarray:
         out = np.zeros(self.m, dtype=np.int64)
-        self._check(self.lib.lpg_get_basis(self._ctx, out.ctypes.data_as(L.c_int64_p)), "lpg_get_basis")
+        self._check(self.lib.lpg_get_basis(self._h, out.ctypes.data_as(L.c_int64_p)), "lpg_get_basis")
         return out
 
     def get_column0(self) -> np.ndarray:
         out = np.zeros(self.info.nrows, dtype=np.float64)
-        self._check(self.lib.lpg_get_column0(self._ctx, out.ctypes.data_as(L.c_double_p)), "lpg_get_column0")
+        self._check(self.lib.lpg_get_column0(self._h, out.ctypes.data_as(L.c_double_p)), "lpg_get_column0")
         return out
 
     def get_log(self):
-        n = self._check(self.lib.lpg_get_log(self._ctx, None, None, 0), "lpg_get_log")
+        n = self._check(self.lib.lpg_get_log(self._h, None, None, 0), "lpg_get_log")
         k = np.zeros(max(n, 1), dtype=np.int64)
         r = np.zeros(max(n, 1), dtype=np.int64)
-        self._check(self.lib.lpg_get_log(self._ctx, k.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_int64_p), n),
+        self._check(self.lib.lpg_get_log(self._h, k.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_int64_p), n),
                     "lpg_get_log")
         return k[:n], r[:n]
 
     # -- timing ----------------------------------------------------------
     def set_timing(self, enable: bool):
-        self._check(self.lib.lpg_set_timing(self._ctx, int(enable)), "lpg_set_timing")
+        self._check(self.lib.lpg_set_timing(self._h, int(enable)), "lpg_set_timing")
 
     def get_timing(self) -> L.Timing:
         t = L.Timing()
-        self._check(self.lib.lpg_get_timing(self._ctx, ctypes.byref(t)), "lpg_get_timing")
+        self._check(self.lib.lpg_get_timing(self._h, ctypes.byref(t)), "lpg_get_timing")
         return t
 
 
-class BatchEngine:
+class BatchEngine(_Handle):
     """`count` LPs of one shape, each an (m+1) x ncols tableau, solved in one
     launch with one workgroup per LP (include/lpg.h, "batches"). ``big_m=True``:
     a Big-M batch, (m+2) x ncols tableaus (row m the M part, row m + 1 the real
@@ -324,6 +346,9 @@ class BatchEngine:
     round of launches, every LP bit for bit what it computes alone. Its methods
     take and return one array per LP (RaggedBatchEngine)."""
 
+    _prefix, _info_type = "lpg_batch", L.BatchInfo
+    _b = property(lambda self: self._h)      # the tests call the library on the handle directly
+
     @staticmethod
     def ragged(shapes, device: int = 0, big_m: bool = False, flags: int = 0, lib=None) -> "RaggedBatchEngine":
         """A batch of len(shapes) LPs, LP q of shapes[q] = (m, ncols)."""
@@ -332,50 +357,17 @@ class BatchEngine:
     def __init__(self, count: int, m: int, ncols: int, device: int = 0, flags: int = 0, lib=None, big_m: bool = False,
                  _handle=None, levels: int = None):
         """``_handle``: an lpg_batch of this shape that the library already made (branch()); the engine owns it."""
-        self.lib = lib if lib is not None else L.load()
-        self._b = ctypes.c_void_p() if _handle is None else _handle
+        self._open(lib, _handle)
         if levels is not None and big_m:
             raise LPGError("BatchEngine: big_m and levels exclude each other (a goal batch of 2 levels is no Big-M batch)")
         if _handle is None:
             if levels is not None:
-                name = "lpg_batch_create_goal"
-                rc = self.lib.lpg_batch_create_goal(ctypes.byref(self._b), device, count, m, ncols, levels, flags)
+                self._create("lpg_batch_create_goal", device, count, m, ncols, levels, flags)
             else:
-                name = "lpg_batch_create_big_m" if big_m else "lpg_batch_create"
-                rc = getattr(self.lib, name)(ctypes.byref(self._b), device, count, m, ncols, flags)
-            if rc != 0:
-                raise LPGError(f"{name} rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+                self._create("lpg_batch_create_big_m" if big_m else "lpg_batch_create", device, count, m, ncols, flags)
         self.count, self.m, self.ncols = count, m, ncols
         self.nobj = levels if levels is not None else (2 if big_m else 1)
         self.levels = levels
-
-    def close(self):
-        if self._b:
-            self.lib.lpg_batch_destroy(self._b)
-            self._b = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_batch_last_error(self._b).decode()}")
-        return rc
-
-    @property
-    def info(self) -> L.BatchInfo:
-        i = L.BatchInfo()
-        self._check(self.lib.lpg_batch_info(self._b, ctypes.byref(i)), "lpg_batch_info")
-        return i
 
     # -- loading ---------------------------------------------------------
     def load(self, T: np.ndarray, basis=None, first: int = 0):
@@ -390,31 +382,31 @@ class BatchEngine:
             if basis.shape != (T.shape[0], self.m):
                 raise LPGError(f"load: basis of shape {basis.shape}, want [{T.shape[0]}, {self.m}]")
             bp = basis.ctypes.data_as(L.c_int64_p)
-        self._check(self.lib.lpg_batch_load(self._b, first, T.shape[0], T.ctypes.data_as(L.c_double_p), self.ncols, bp),
+        self._check(self.lib.lpg_batch_load(self._h, first, T.shape[0], T.ctypes.data_as(L.c_double_p), self.ncols, bp),
                     "lpg_batch_load")
 
     def generate(self, n: int, seed: int = 20220518, kind: int = L.GEN_DENSE):
         """LP b = Engine.generate(n, seed + b, kind)."""
-        self._check(self.lib.lpg_batch_generate(self._b, n, seed, kind), "lpg_batch_generate")
+        self._check(self.lib.lpg_batch_generate(self._h, n, seed, kind), "lpg_batch_generate")
 
     def set_tolerances(self, eps_piv=1e-9, eps_opt=1e-9):
-        self._check(self.lib.lpg_batch_set_tolerances(self._b, eps_piv, eps_opt), "lpg_batch_set_tolerances")
+        self._check(self.lib.lpg_batch_set_tolerances(self._h, eps_piv, eps_opt), "lpg_batch_set_tolerances")
 
     def set_active_columns(self, nact: int):
-        self._check(self.lib.lpg_batch_set_active_columns(self._b, nact), "lpg_batch_set_active_columns")
+        self._check(self.lib.lpg_batch_set_active_columns(self._h, nact), "lpg_batch_set_active_columns")
 
     def reserve_log(self, n: int):
-        self._check(self.lib.lpg_batch_reserve_log(self._b, n), "lpg_batch_reserve_log")
+        self._check(self.lib.lpg_batch_reserve_log(self._h, n), "lpg_batch_reserve_log")
 
     # -- pivoting --------------------------------------------------------
     def solve(self, max_pivots: int = 1 << 40, rule: int = L.RULE_DANTZIG) -> list:
         r = (L.Result * self.count)()
-        self._check(self.lib.lpg_batch_solve(self._b, max_pivots, rule, r), "lpg_batch_solve")
+        self._check(self.lib.lpg_batch_solve(self._h, max_pivots, rule, r), "lpg_batch_solve")
         return [_res(x) for x in r]
 
     def solve_dual(self, max_pivots: int = 1 << 40) -> list:
         r = (L.Result * self.count)()
-        self._check(self.lib.lpg_batch_solve_dual(self._b, max_pivots, r), "lpg_batch_solve_dual")
+        self._check(self.lib.lpg_batch_solve_dual(self._h, max_pivots, r), "lpg_batch_solve_dual")
         return [_res(x) for x in r]
 
     def _costs(self, cost, what):
@@ -432,7 +424,7 @@ class BatchEngine:
         (the row pitch is the array's width). Afterwards columns 1..art_first-1 are active."""
         keep, cp, ld = (None, None, 0) if cost is None else self._costs(cost, "solve_two_phase")
         r = (L.Result * self.count)()
-        self._check(self.lib.lpg_batch_solve_two_phase(self._b, art_first, cp, ld, max_pivots, rule, r),
+        self._check(self.lib.lpg_batch_solve_two_phase(self._h, art_first, cp, ld, max_pivots, rule, r),
                     "lpg_batch_solve_two_phase")
         del keep
         return [_res(x) for x in r]
@@ -442,7 +434,7 @@ class BatchEngine:
         Another call goes on where a budget-limited one stopped."""
         keep, cp, ld = (None, None, 0) if cost is None else self._costs(cost, "solve_big_m")
         r = (L.Result * self.count)()
-        self._check(self.lib.lpg_batch_solve_big_m(self._b, art_first, cp, ld, max_pivots, rule, r),
+        self._check(self.lib.lpg_batch_solve_big_m(self._h, art_first, cp, ld, max_pivots, rule, r),
                     "lpg_batch_solve_big_m")
         del keep
         return [_res(x) for x in r]
@@ -461,7 +453,7 @@ class BatchEngine:
             raise LPGError(f"solve_goal: costs of shape {c.shape}, want [{self.count}, {K}, >= {self.ncols - 1}]")
         r = (L.Result * self.count)()
         attain = np.zeros((self.count, K), dtype=np.float64)
-        self._check(self.lib.lpg_batch_solve_goal(self._b, c.ctypes.data_as(L.c_double_p), K * c.shape[2], c.shape[2],
+        self._check(self.lib.lpg_batch_solve_goal(self._h, c.ctypes.data_as(L.c_double_p), K * c.shape[2], c.shape[2],
                                                   max_pivots, rule, r, attain.ctypes.data_as(L.c_double_p)),
                     "lpg_batch_solve_goal")
         return [_res(x) for x in r], attain
@@ -469,13 +461,13 @@ class BatchEngine:
     def set_objective(self, cost):
         """Engine.set_objective on every LP; cost: [N] or [count, >= N]."""
         keep, cp, ld = self._costs(cost, "set_objective")
-        self._check(self.lib.lpg_batch_set_objective(self._b, cp, ld), "lpg_batch_set_objective")
+        self._check(self.lib.lpg_batch_set_objective(self._h, cp, ld), "lpg_batch_set_objective")
         del keep
 
     def generate_artificial(self, n: int, seed: int = 20220518) -> int:
         """LP b = Engine.generate(n, seed + b, GEN_ARTIFICIAL); returns art_first."""
         af = ctypes.c_int64(0)
-        self._check(self.lib.lpg_batch_generate_artificial(self._b, n, seed, ctypes.byref(af)),
+        self._check(self.lib.lpg_batch_generate_artificial(self._h, n, seed, ctypes.byref(af)),
                     "lpg_batch_generate_artificial")
         return int(af.value)
 
@@ -483,22 +475,22 @@ class BatchEngine:
     def get_rows(self, first: int = 0, n: int = None) -> np.ndarray:
         n = self.count - first if n is None else n
         out = np.zeros((n, self.m + self.nobj, self.ncols), dtype=np.float64)
-        self._check(self.lib.lpg_batch_get_rows(self._b, first, n, out.ctypes.data_as(L.c_double_p), self.ncols),
+        self._check(self.lib.lpg_batch_get_rows(self._h, first, n, out.ctypes.data_as(L.c_double_p), self.ncols),
                     "lpg_batch_get_rows")
         return out
 
     def get_basis(self, first: int = 0, n: int = None) -> np.ndarray:
         n = self.count - first if n is None else n
         out = np.zeros((n, self.m), dtype=np.int64)
-        self._check(self.lib.lpg_batch_get_basis(self._b, first, n, out.ctypes.data_as(L.c_int64_p)),
+        self._check(self.lib.lpg_batch_get_basis(self._h, first, n, out.ctypes.data_as(L.c_int64_p)),
                     "lpg_batch_get_basis")
         return out
 
     def get_log(self, lp: int):
-        n = self._check(self.lib.lpg_batch_get_log(self._b, lp, None, None, 0), "lpg_batch_get_log")
+        n = self._check(self.lib.lpg_batch_get_log(self._h, lp, None, None, 0), "lpg_batch_get_log")
         k = np.zeros(max(n, 1), dtype=np.int64)
         r = np.zeros(max(n, 1), dtype=np.int64)
-        self._check(self.lib.lpg_batch_get_log(self._b, lp, k.ctypes.data_as(L.c_int64_p),
+        self._check(self.lib.lpg_batch_get_log(self._h, lp, k.ctypes.data_as(L.c_int64_p),
                                                r.ctypes.data_as(L.c_int64_p), n), "lpg_batch_get_log")
         return k[:n], r[:n]
 
@@ -506,7 +498,7 @@ class BatchEngine:
     def active_columns(self, lp: int = 0):
         """(nact, art_first) of LP lp: its priced columns 1..nact, and a ragged batch's recorded art_first."""
         nact, af = ctypes.c_int64(0), ctypes.c_int64(0)
-        self._check(self.lib.lpg_batch_active_columns(self._b, lp, ctypes.byref(nact), ctypes.byref(af)),
+        self._check(self.lib.lpg_batch_active_columns(self._h, lp, ctypes.byref(nact), ctypes.byref(af)),
                     "lpg_batch_active_columns")
         return int(nact.value), int(af.value)
 
@@ -516,7 +508,7 @@ class BatchEngine:
         (row, col, value), one entry per LP; row = col = -1 where every integer column is integral."""
         mk, mp, nmask, ld = self._mask(mask, "branch_select")
         out = (L.Branch * self.count)()
-        self._check(self.lib.lpg_batch_branch_select(self._b, mp, nmask, ld, int_tol, rule, out), "lpg_batch_branch_select")
+        self._check(self.lib.lpg_batch_branch_select(self._h, mp, nmask, ld, int_tol, rule, out), "lpg_batch_branch_select")
         a = np.frombuffer(out, dtype=np.dtype([("row", np.int64), ("col", np.int64), ("value", np.float64)]))
         return a["row"].copy(), a["col"].copy(), a["value"].copy()
 
@@ -530,7 +522,7 @@ class BatchEngine:
         if src.ndim != 1 or row.shape != src.shape or d.shape != src.shape:
             raise LPGError(f"branch: src, row, dir of shapes {src.shape}, {row.shape}, {d.shape}, want three [n]")
         child = ctypes.c_void_p()
-        self._check(self.lib.lpg_batch_branch(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
+        self._check(self.lib.lpg_batch_branch(ctypes.byref(child), self._h, src.shape[0], src.ctypes.data_as(L.c_int64_p),
                                               row.ctypes.data_as(L.c_int64_p), d.ctypes.data_as(L.c_int8_p)),
                     "lpg_batch_branch")
         return self._wrap_child(child, src, [1] * len(src))
@@ -561,7 +553,7 @@ class BatchEngine:
         mk, mp, nmask, ld = self._mask(mask, "cut_select")
         ncut = np.zeros(self.count, dtype=np.int64)
         rows = np.zeros((self.count, max(int(max_cuts), 1)), dtype=np.int64)
-        self._check(self.lib.lpg_batch_cut_select(self._b, mp, nmask, ld, int_tol, max_cuts, ncut.ctypes.data_as(L.c_int64_p),
+        self._check(self.lib.lpg_batch_cut_select(self._h, mp, nmask, ld, int_tol, max_cuts, ncut.ctypes.data_as(L.c_int64_p),
                                                   rows.ctypes.data_as(L.c_int64_p)), "lpg_batch_cut_select")
         return [rows[q, :ncut[q]].copy() for q in range(self.count)]
 
@@ -581,7 +573,7 @@ class BatchEngine:
             rows = np.zeros(1, dtype=np.int64)           # a pointer to pass; the library refuses the empty interval
         mk, mp, nmask, ld = self._mask(mask, "cut")
         child = ctypes.c_void_p()
-        self._check(self.lib.lpg_batch_cut(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
+        self._check(self.lib.lpg_batch_cut(ctypes.byref(child), self._h, src.shape[0], src.ctypes.data_as(L.c_int64_p),
                                            first.ctypes.data_as(L.c_int64_p), rows.ctypes.data_as(L.c_int64_p), mp, nmask, ld),
                     "lpg_batch_cut")
         return self._wrap_child(child, src, [len(r) for r in per])
@@ -613,7 +605,7 @@ class BatchEngine:
             raise LPGError(f"scenario: src of shape {src.shape}, want [n]")
         idt, r = self._ident(ident, "scenario"), self._rhs(rhs, src, "scenario")
         child = ctypes.c_void_p()
-        self._check(self.lib.lpg_batch_scenario(ctypes.byref(child), self._b, src.shape[0], src.ctypes.data_as(L.c_int64_p),
+        self._check(self.lib.lpg_batch_scenario(ctypes.byref(child), self._h, src.shape[0], src.ctypes.data_as(L.c_int64_p),
                                                 idt.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_double_p)),
                     "lpg_batch_scenario")
         return self._wrap_child(child, src, [0] * len(src))
@@ -622,7 +614,7 @@ class BatchEngine:
         """Every LP's column 0 restated in place for its new right-hand side rhs[q] (include/lpg.h
         lpg_batch_set_rhs); ident as scenario's, of this batch. The LPs start again as after load()."""
         idt, r = self._ident(ident, "set_rhs"), self._rhs(rhs, range(self.count), "set_rhs")
-        self._check(self.lib.lpg_batch_set_rhs(self._b, idt.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_double_p)),
+        self._check(self.lib.lpg_batch_set_rhs(self._h, idt.ctypes.data_as(L.c_int64_p), r.ctypes.data_as(L.c_double_p)),
                     "lpg_batch_set_rhs")
 
     # -- ranging ---------------------------------------------------------
@@ -639,7 +631,7 @@ class BatchEngine:
             ints = f.endswith("_at")
             flat[f] = np.zeros(nc if f.startswith("cost") else nb, dtype=np.int64 if ints else np.float64)
             setattr(out, f, flat[f].ctypes.data_as(L.c_int64_p if ints else L.c_double_p))
-        self._check(self.lib.lpg_batch_ranging(self._b, idt.ctypes.data_as(L.c_int64_p), ctypes.byref(out)),
+        self._check(self.lib.lpg_batch_ranging(self._h, idt.ctypes.data_as(L.c_int64_p), ctypes.byref(out)),
                     "lpg_batch_ranging")
         return flat
 
@@ -664,8 +656,7 @@ class RaggedBatchEngine(BatchEngine):
     lds_bytes). The packing to and from the C ABI's flat arrays happens here."""
 
     def __init__(self, shapes, device: int = 0, big_m: bool = False, flags: int = 0, lib=None, _handle=None):
-        self.lib = lib if lib is not None else L.load()
-        self._b = ctypes.c_void_p() if _handle is None else _handle
+        self._open(lib, _handle)
         try:
             self.shapes = [(int(m), int(nc)) for m, nc in shapes]
         except (TypeError, ValueError) as e:
@@ -674,10 +665,8 @@ class RaggedBatchEngine(BatchEngine):
         ms = np.array([m for m, _ in self.shapes], dtype=np.int64)
         ncs = np.array([nc for _, nc in self.shapes], dtype=np.int64)
         if _handle is None:
-            rc = self.lib.lpg_batch_create_ragged(ctypes.byref(self._b), device, self.count, ms.ctypes.data_as(L.c_int64_p),
-                                                  ncs.ctypes.data_as(L.c_int64_p), self.nobj, flags)
-            if rc != 0:
-                raise LPGError(f"lpg_batch_create_ragged rc={rc}: {self.lib.lpg_batch_last_error(None).decode()}")
+            self._create("lpg_batch_create_ragged", device, self.count, ms.ctypes.data_as(L.c_int64_p),
+                         ncs.ctypes.data_as(L.c_int64_p), self.nobj, flags)
         self.m, self.ncols = int(ms.max()), int(ncs.max())
 
     def _shape_of(self, q):
@@ -685,7 +674,7 @@ class RaggedBatchEngine(BatchEngine):
 
     def shape(self, lp: int) -> L.BatchShape:
         s = L.BatchShape()
-        self._check(self.lib.lpg_batch_shape(self._b, lp, ctypes.byref(s)), "lpg_batch_shape")
+        self._check(self.lib.lpg_batch_shape(self._h, lp, ctypes.byref(s)), "lpg_batch_shape")
         return s
 
     def _flat(self, arrays, what, shape_of, dtype):
@@ -717,7 +706,7 @@ class RaggedBatchEngine(BatchEngine):
         if bases is not None:
             bas = self._flat(bases, "load (bases)", lambda m, nc: (m,), np.int64)
             bp = bas.ctypes.data_as(L.c_int64_p)
-        self._check(self.lib.lpg_batch_load_packed(self._b, 0, self.count, T.ctypes.data_as(L.c_double_p), bp),
+        self._check(self.lib.lpg_batch_load_packed(self._h, 0, self.count, T.ctypes.data_as(L.c_double_p), bp),
                     "lpg_batch_load_packed")
 
     def _packed_costs(self, costs, what):
@@ -738,7 +727,7 @@ class RaggedBatchEngine(BatchEngine):
         af = self._art(art_first, "solve_two_phase")
         keep, cp = self._packed_costs(costs, "solve_two_phase")
         r = (L.Result * self.count)()
-        self._check(self.lib.lpg_batch_solve_two_phase_ragged(self._b, af.ctypes.data_as(L.c_int64_p), cp, max_pivots, rule,
+        self._check(self.lib.lpg_batch_solve_two_phase_ragged(self._h, af.ctypes.data_as(L.c_int64_p), cp, max_pivots, rule,
                                                               r), "lpg_batch_solve_two_phase_ragged")
         del keep
         return [_res(x) for x in r]
@@ -748,7 +737,7 @@ class RaggedBatchEngine(BatchEngine):
         af = self._art(art_first, "solve_big_m")
         keep, cp = self._packed_costs(costs, "solve_big_m")
         r = (L.Result * self.count)()
-        self._check(self.lib.lpg_batch_solve_big_m_ragged(self._b, af.ctypes.data_as(L.c_int64_p), cp, max_pivots, rule, r),
+        self._check(self.lib.lpg_batch_solve_big_m_ragged(self._h, af.ctypes.data_as(L.c_int64_p), cp, max_pivots, rule, r),
                     "lpg_batch_solve_big_m_ragged")
         del keep
         return [_res(x) for x in r]
@@ -756,7 +745,7 @@ class RaggedBatchEngine(BatchEngine):
     def set_objective(self, costs):
         """Engine.set_objective on every LP; costs[q]: [ncols_q - 1]."""
         keep, cp = self._packed_costs(costs, "set_objective")
-        self._check(self.lib.lpg_batch_set_objective_packed(self._b, cp), "lpg_batch_set_objective_packed")
+        self._check(self.lib.lpg_batch_set_objective_packed(self._h, cp), "lpg_batch_set_objective_packed")
         del keep
 
     def _ident(self, ident, what):
@@ -782,85 +771,52 @@ class RaggedBatchEngine(BatchEngine):
 
     def get_rows(self) -> list:
         flat = np.zeros(sum((m + self.nobj) * nc for m, nc in self.shapes), dtype=np.float64)
-        self._check(self.lib.lpg_batch_get_rows_packed(self._b, 0, self.count, flat.ctypes.data_as(L.c_double_p)),
+        self._check(self.lib.lpg_batch_get_rows_packed(self._h, 0, self.count, flat.ctypes.data_as(L.c_double_p)),
                     "lpg_batch_get_rows_packed")
         return self._split(flat, lambda m, nc: (m + self.nobj, nc))
 
     def get_basis(self) -> list:
         flat = np.zeros(sum(m for m, _ in self.shapes), dtype=np.int64)
-        self._check(self.lib.lpg_batch_get_basis_packed(self._b, 0, self.count, flat.ctypes.data_as(L.c_int64_p)),
+        self._check(self.lib.lpg_batch_get_basis_packed(self._h, 0, self.count, flat.ctypes.data_as(L.c_int64_p)),
                     "lpg_batch_get_basis_packed")
         return self._split(flat, lambda m, nc: (m,))
 
 
 @dataclass
-class AssignResult:
+class AssignResult(_HasStatus):
     status: int
     steps: int
     objective: float
 
-    @property
-    def status_name(self) -> str:
-        return L.STATUS_NAMES.get(self.status, str(self.status))
 
-
-class AssignmentBatch:
+class AssignmentBatch(_Handle):
     """`count` assignment problems of one shape, nr x nc cost matrices with
     nr <= nc, solved in one launch by the Hungarian method (include/lpg.h,
     "assignment"): every row gets a distinct column, the chosen costs sum to the
     minimum (``maximize=True``: the maximum); +inf forbids a pair."""
 
+    _prefix, _info_type = "lpg_assign", L.AssignInfo
+
     def __init__(self, count: int, nr: int, nc: int, device: int = 0, maximize: bool = False, lib=None):
-        self.lib = lib if lib is not None else L.load()
-        self._a = ctypes.c_void_p()
-        rc = self.lib.lpg_assign_create(ctypes.byref(self._a), device, count, nr, nc, L.ASSIGN_MAXIMIZE if maximize else 0)
-        if rc != 0:
-            raise LPGError(f"lpg_assign_create rc={rc}: {self.lib.lpg_assign_last_error(None).decode()}")
+        self._open(lib)
+        self._create("lpg_assign_create", device, count, nr, nc, L.ASSIGN_MAXIMIZE if maximize else 0)
         self.count, self.nr, self.nc, self.maximize = count, nr, nc, bool(maximize)
-
-    def close(self):
-        if self._a:
-            self.lib.lpg_assign_destroy(self._a)
-            self._a = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_assign_last_error(self._a).decode()}")
-        return rc
-
-    @property
-    def info(self) -> L.AssignInfo:
-        i = L.AssignInfo()
-        self._check(self.lib.lpg_assign_info(self._a, ctypes.byref(i)), "lpg_assign_info")
-        return i
 
     def load(self, costs: np.ndarray, first: int = 0):
         """costs: [n, nr, nc]; problems first .. first + n - 1."""
         c = np.ascontiguousarray(costs, dtype=np.float64)
         if c.ndim != 3 or c.shape[1] != self.nr or c.shape[2] != self.nc:
             raise LPGError(f"load: costs of shape {c.shape}, want [n, {self.nr}, {self.nc}]")
-        self._check(self.lib.lpg_assign_load(self._a, first, c.shape[0], c.ctypes.data_as(L.c_double_p), self.nc),
+        self._check(self.lib.lpg_assign_load(self._h, first, c.shape[0], c.ctypes.data_as(L.c_double_p), self.nc),
                     "lpg_assign_load")
 
     def generate(self, seed: int = 20220518, range: int = 100):
         """Problem q, entry (i, j) = floor(uniform01(seed + q, i * nc + j) * range)."""
-        self._check(self.lib.lpg_assign_generate(self._a, seed, range), "lpg_assign_generate")
+        self._check(self.lib.lpg_assign_generate(self._h, seed, range), "lpg_assign_generate")
 
     def solve(self) -> list:
         r = (L.AssignResult * self.count)()
-        self._check(self.lib.lpg_assign_solve(self._a, r), "lpg_assign_solve")
+        self._check(self.lib.lpg_assign_solve(self._h, r), "lpg_assign_solve")
         return [AssignResult(x.status, x.steps, x.objective) for x in r]
 
     def get(self, first: int = 0, n: int = None):
@@ -869,72 +825,38 @@ class AssignmentBatch:
         col = np.empty((n, self.nr), dtype=np.int64)
         u = np.empty((n, self.nr), dtype=np.float64)
         v = np.empty((n, self.nc), dtype=np.float64)
-        self._check(self.lib.lpg_assign_get(self._a, first, n, col.ctypes.data_as(L.c_int64_p),
+        self._check(self.lib.lpg_assign_get(self._h, first, n, col.ctypes.data_as(L.c_int64_p),
                                             u.ctypes.data_as(L.c_double_p), v.ctypes.data_as(L.c_double_p)),
                     "lpg_assign_get")
         return col, u, v
 
 
 @dataclass
-class BinaryResult:
+class BinaryResult(_HasStatus):
     status: int
     found: int
     nodes: int
     objective: float
 
-    @property
-    def status_name(self) -> str:
-        return L.STATUS_NAMES.get(self.status, str(self.status))
 
-
-class BinaryBatch:
+class BinaryBatch(_Handle):
     """`count` 0-1 programs of one shape, m rows and n <= 64 binary variables,
     solved by implicit enumeration on the device (include/lpg.h, "0-1
     programs"): minimise (``maximize=True``: maximise) c.x subject to a_i.x
     {<=, =, >=} b_i on integer data; 2^split independent sub-searches per problem."""
 
+    _prefix, _info_type = "lpg_binary", L.BinaryInfo
+
     def __init__(self, count: int, m: int, n: int, split: int = 0, maximize: bool = False, device: int = 0, lib=None):
-        self.lib = lib if lib is not None else L.load()
-        self._b = ctypes.c_void_p()
-        rc = self.lib.lpg_binary_create(ctypes.byref(self._b), device, count, m, n, split,
-                                        L.BINARY_MAXIMIZE if maximize else 0)
-        if rc != 0:
-            raise LPGError(f"lpg_binary_create rc={rc}: {self.lib.lpg_binary_last_error(None).decode()}")
+        self._open(lib)
+        self._create("lpg_binary_create", device, count, m, n, split, L.BINARY_MAXIMIZE if maximize else 0)
         self.count, self.m, self.n, self.split, self.maximize = count, m, n, split, bool(maximize)
-
-    def close(self):
-        if self._b:
-            self.lib.lpg_binary_destroy(self._b)
-            self._b = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_binary_last_error(self._b).decode()}")
-        return rc
-
-    @property
-    def info(self) -> L.BinaryInfo:
-        i = L.BinaryInfo()
-        self._check(self.lib.lpg_binary_info(self._b, ctypes.byref(i)), "lpg_binary_info")
-        return i
 
     @property
     def resident_waves(self) -> int:
         """The waves of this batch's kernel that the device holds at once (the occupancy query)."""
         w = ctypes.c_int64()
-        self._check(self.lib.lpg_binary_occupancy(self._b, ctypes.byref(w)), "lpg_binary_occupancy")
+        self._check(self.lib.lpg_binary_occupancy(self._h, ctypes.byref(w)), "lpg_binary_occupancy")
         return int(w.value)
 
     def load(self, A, sense, rhs, c, first: int = 0):
@@ -947,44 +869,42 @@ class BinaryBatch:
         if A.shape != (k, self.m, self.n) or sense.shape != (k, self.m) or rhs.shape != (k, self.m) or c.shape != (k, self.n):
             raise LPGError(f"load: shapes {A.shape}, {sense.shape}, {rhs.shape}, {c.shape}, want [k, {self.m}, {self.n}], "
                            f"[k, {self.m}], [k, {self.m}], [k, {self.n}]")
-        self._check(self.lib.lpg_binary_load(self._b, first, k, A.ctypes.data_as(L.c_double_p), self.n,
+        self._check(self.lib.lpg_binary_load(self._h, first, k, A.ctypes.data_as(L.c_double_p), self.n,
                                              sense.ctypes.data_as(L.c_int32_p), rhs.ctypes.data_as(L.c_double_p),
                                              c.ctypes.data_as(L.c_double_p)), "lpg_binary_load")
 
     def generate(self, seed: int = 20220518, kind: int = L.BINARY_GEN_BANDED):
         """The banded planted problems of include/lpg.h ("Generator"), problem q from seed + q."""
-        self._check(self.lib.lpg_binary_generate(self._b, seed, kind), "lpg_binary_generate")
+        self._check(self.lib.lpg_binary_generate(self._h, seed, kind), "lpg_binary_generate")
 
     def solve(self, max_nodes: int = 0) -> list:
         """Continues every search, by at most max_nodes nodes per sub-search (0: to the end)."""
         r = (L.BinaryResult * self.count)()
-        self._check(self.lib.lpg_binary_solve(self._b, max_nodes, r), "lpg_binary_solve")
+        self._check(self.lib.lpg_binary_solve(self._h, max_nodes, r), "lpg_binary_solve")
         return [BinaryResult(x.status, x.found, x.nodes, x.objective) for x in r]
 
     def get(self, first: int = 0, n: int = None) -> np.ndarray:
         """x [n, self.n] int8 of problems first .. first + n - 1 after a solve; -1 throughout where nothing was found."""
         n = self.count - first if n is None else n
         x = np.empty((n, self.n), dtype=np.int8)
-        self._check(self.lib.lpg_binary_get(self._b, first, n, x.ctypes.data_as(L.c_int8_p)), "lpg_binary_get")
+        self._check(self.lib.lpg_binary_get(self._h, first, n, x.ctypes.data_as(L.c_int8_p)), "lpg_binary_get")
         return x
 
 
 @dataclass
-class TransportResult:
+class TransportResult(_HasStatus):
     status: int
     iterations: int
     objective: float
 
-    @property
-    def status_name(self) -> str:
-        return L.STATUS_NAMES.get(self.status, str(self.status))
 
-
-class TransportBatch:
+class TransportBatch(_Handle):
     """`count` balanced transportation problems of one shape, nr sources by nc
     sinks, solved on the device by the tableau method (include/lpg.h,
     "transportation"): a least-cost or northwest-corner start, potentials,
     pricing and the closed loop. Costs, supplies and demands are integers."""
+
+    _prefix, _info_type = "lpg_transport", L.TransportInfo
 
     STARTS = {"least_cost": L.TRANSPORT_START_LEAST_COST, "northwest": L.TRANSPORT_START_NORTHWEST}
 
@@ -992,41 +912,9 @@ class TransportBatch:
                  lib=None):
         if start not in self.STARTS:
             raise LPGError(f"TransportBatch: start {start!r}, want 'least_cost' or 'northwest'")
-        self.lib = lib if lib is not None else L.load()
-        self._t = ctypes.c_void_p()
-        flags = (L.TRANSPORT_MAXIMIZE if maximize else 0) | self.STARTS[start]
-        rc = self.lib.lpg_transport_create(ctypes.byref(self._t), device, count, nr, nc, flags)
-        if rc != 0:
-            raise LPGError(f"lpg_transport_create rc={rc}: {self.lib.lpg_transport_last_error(None).decode()}")
+        self._open(lib)
+        self._create("lpg_transport_create", device, count, nr, nc, (L.TRANSPORT_MAXIMIZE if maximize else 0) | self.STARTS[start])
         self.count, self.nr, self.nc, self.maximize, self.start = count, nr, nc, bool(maximize), start
-
-    def close(self):
-        if self._t:
-            self.lib.lpg_transport_destroy(self._t)
-            self._t = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise LPGError(f"{what} rc={rc}: {self.lib.lpg_transport_last_error(self._t).decode()}")
-        return rc
-
-    @property
-    def info(self) -> L.TransportInfo:
-        i = L.TransportInfo()
-        self._check(self.lib.lpg_transport_info(self._t, ctypes.byref(i)), "lpg_transport_info")
-        return i
 
     def load(self, costs, supply, demand, first: int = 0):
         """costs [n, nr, nc], supply [n, nr], demand [n, nc]: problems first .. first + n - 1."""
@@ -1037,20 +925,20 @@ class TransportBatch:
         if c.shape != (n, self.nr, self.nc) or s.shape != (n, self.nr) or d.shape != (n, self.nc):
             raise LPGError(f"load: shapes {c.shape}, {s.shape}, {d.shape}, want [n, {self.nr}, {self.nc}], "
                            f"[n, {self.nr}], [n, {self.nc}]")
-        self._check(self.lib.lpg_transport_load(self._t, first, n, c.ctypes.data_as(L.c_double_p), self.nc,
+        self._check(self.lib.lpg_transport_load(self._h, first, n, c.ctypes.data_as(L.c_double_p), self.nc,
                                                 s.ctypes.data_as(L.c_double_p), d.ctypes.data_as(L.c_double_p)),
                     "lpg_transport_load")
 
     def generate(self, seed: int = 20220518, range: int = 100, qmax: int = 9):
         """The generated problems of include/lpg.h ("Generator"), problem q from seed + q."""
-        self._check(self.lib.lpg_transport_generate(self._t, seed, range, qmax), "lpg_transport_generate")
+        self._check(self.lib.lpg_transport_generate(self._h, seed, range, qmax), "lpg_transport_generate")
 
     def solve(self, max_iters: int = None, rule: int = L.RULE_DANTZIG) -> list:
         """Continues every problem by at most max_iters iterations (default 50 (nr + nc))."""
         if max_iters is None:
             max_iters = 50 * (self.nr + self.nc)
         r = (L.TransportResult * self.count)()
-        self._check(self.lib.lpg_transport_solve(self._t, max_iters, rule, r), "lpg_transport_solve")
+        self._check(self.lib.lpg_transport_solve(self._h, max_iters, rule, r), "lpg_transport_solve")
         return [TransportResult(x.status, x.iterations, x.objective) for x in r]
 
     def get(self, first: int = 0, n: int = None):
@@ -1060,7 +948,7 @@ class TransportBatch:
         u = np.empty((n, self.nr), dtype=np.float64)
         v = np.empty((n, self.nc), dtype=np.float64)
         basis = np.empty((n, self.nr + self.nc - 1), dtype=np.int64)
-        self._check(self.lib.lpg_transport_get(self._t, first, n, x.ctypes.data_as(L.c_double_p),
+        self._check(self.lib.lpg_transport_get(self._h, first, n, x.ctypes.data_as(L.c_double_p),
                                                u.ctypes.data_as(L.c_double_p), v.ctypes.data_as(L.c_double_p),
                                                basis.ctypes.data_as(L.c_int64_p)), "lpg_transport_get")
         return x, u, v, basis
